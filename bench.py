@@ -17,12 +17,28 @@ oracle run over a sample of the whole group (``parity``).  Strong scaling:
 ``--shard morton`` replicates the background instead; ``--shard group``
 gives every rank its own group (weak scaling, ParMmg's per-group sharding).
 
-After the timed steps (rank 0, N = 1): the CPU baseline runs the oracle — a C
-restatement of the reference path — over ALL new points in the reference's
-visitation order on the host cores, and the GPU outputs of the last step are
-checked against that same run point by point (``parity``: class (i) identity,
-acceptance of every chosen element, values of the reference interpolator in
-it, bit-exact count and max relative error).
+A plain run does what the headline figure needs and nothing else: it builds
+the workload, uploads it, runs the warmup steps, times ``--steps`` steps
+(``ms_per_step`` = wall time of the timed region / steps), writes the outputs
+of the last timed step when ``--dump-outputs DIR`` is given, and prints the
+result line.  Everything else is behind ``--full``: the per-step HIP event
+means (the same steps again, each read back), the side legs (host-buffer call,
+surface branch alone, renumbered points, tetra quality, device snapshot, many
+groups per call, the graded cfgG meshes; each with its own ``--no-...``
+switch), for N > 1 the all-gather timing and the check of the gathered
+results, and (rank 0, N = 1) the CPU baseline: the oracle — a C restatement of
+the reference path — over ALL new points in the reference's visitation order
+on the host cores, with the GPU outputs of the last step checked against that
+same run point by point (``parity``: class (i) identity, acceptance of every
+chosen element, values of the reference interpolator in it, bit-exact count
+and max relative error).
+
+``--dump-outputs DIR``: the arrays a caller of the timed step receives (the
+interpolated metric and field rows, the located element and the hit code of
+every point), as ``DIR/<name>.npy`` (float64; ``hit`` float32).  Outputs over
+the size cap are written as a fixed, seeded sample of the processed points
+(``sample_index.npy`` holds their point ids); the workload is seeded, so two
+runs with the same arguments write the rows of the same points.
 
 Prints ONE JSON line (rank 0).
 """
@@ -506,6 +522,49 @@ def iteration2_oracle_check(new_t, mo, fo, w, q2, pc2, out, nsample: int = 20000
             "contract": rep, "ok": bool(ok and lowest + closest == fbc.size)}
 
 
+DUMP_SEED = 20261
+DUMP_CAP_BYTES = 48 << 20  # of all files together (well under 64 MB)
+
+
+def dump_outputs(dirname: str, q_pc, d_mo, d_fo, d_elem, d_hit, suffix: str = "") -> dict:
+    """The outputs of the last timed step as DIR/<name><suffix>.npy: met,
+    field<i>, elem (float64), hit (float32) and sample_index (float64, the
+    point ids of the rows).  Every processed point (class != 0; the step
+    leaves the rows of the others untouched) when that fits DUMP_CAP_BYTES,
+    else a sorted sample of them drawn with DUMP_SEED."""
+    def host(a):  # a DeviceArray, a torch tensor (split modes) or a host array
+        if isinstance(a, np.ndarray):
+            return a
+        return a.download() if hasattr(a, "download") else a.cpu().numpy()
+
+    os.makedirs(dirname, exist_ok=True)
+    cand = np.nonzero(np.asarray(q_pc) != 0)[0]
+    arrays = [("met", d_mo)] + [(f"field{i}", f) for i, f in enumerate(d_fo)]
+    row_bytes = 8 * sum(int(a.shape[1]) for _, a in arrays) + 8 + 4 + 8
+    nmax = DUMP_CAP_BYTES // row_bytes
+    if cand.size > nmax:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(cand, size=nmax, replace=False))
+    else:
+        idx = cand
+    total = 0
+    names = []
+
+    def save(name, a):
+        nonlocal total
+        path = os.path.join(dirname, f"{name}{suffix}.npy")
+        np.save(path, np.ascontiguousarray(a))
+        total += os.path.getsize(path)
+        names.append(os.path.basename(path))
+
+    for name, a in arrays:  # one array on the host at a time
+        save(name, host(a)[idx].astype(np.float64, copy=False))
+    save("elem", host(d_elem)[idx].astype(np.float64))
+    save("hit", host(d_hit)[idx].astype(np.float32))
+    save("sample_index", idx.astype(np.float64))
+    return {"dir": dirname, "files": names, "rows": int(idx.size), "rows_processed": int(cand.size),
+            "sampled": bool(idx.size < cand.size), "seed": DUMP_SEED, "bytes": int(total)}
+
+
 LOCATE_KEYS = ("nvol", "nbdy", "nvol_exact", "nvol_stuck", "nvol_limit", "nvol_noseed", "nvol_exhaust",
                "nvol_closest", "nbdy_exhaust", "nbdy_stale", "nbdy_closest", "stepmax")
 
@@ -763,6 +822,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: per-step HIP event means, the side legs "
+                         "(each with its --no-... switch), the all-gather timing and check of a split, the CPU "
+                         "baseline and the parity check against it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (a seeded sample of the rows "
+                         "when they exceed the size cap)")
     ap.add_argument("--config", default="cfg4", choices=sorted(configs.SHORT))
     ap.add_argument("--sort", default="auto", choices=["auto", "on", "off"],
                     help="query order: Morton binning (on), input order (off), or chosen on the device")
@@ -803,6 +869,8 @@ def main():
     ap.add_argument("--no-graded", action="store_true",
                     help="skip the (separately reported) step on the graded and stretched cfgG meshes")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # PMMG_BENCH_BACKEND=gloo: host-side collectives, ranks share the visible
     # GPUs round-robin (rehearsing several ranks on a one-GPU box)
@@ -925,21 +993,29 @@ def main():
     elapsed = time.perf_counter() - t0
     log(f"[bench r{rank}] timed {args.steps} steps: {1e3 * elapsed / args.steps:.3f} ms/step")
     st_timed = st  # HIP events of the last timed step (the roofline's stage time)
-    # per-stage device times of every step (HIP events): the same K steps
-    # again, each followed by a read of its event times (reported as means)
-    ms_vol, ms_tot, ms_walk = [], [], []
-    for _ in range(args.steps):
-        step()
-        st = ctx.sync()
-        ms_vol.append(st.ms_vol)
-        ms_tot.append(st.ms_total)
-        ms_walk.append(st.ms_vol_locate)
+    dumped = None
+    if args.dump_outputs:
+        t_d = time.perf_counter()
+        dumped = dump_outputs(args.dump_outputs, q_pc, d_mo, d_fo, d_elem, d_hit, f"_r{rank}" if world > 1 else "")
+        log(f"[bench r{rank}] outputs of the last timed step written in {time.perf_counter() - t_d:.1f}s: {dumped}")
+    ms_vol, ms_tot, ms_walk = [st.ms_vol], [st.ms_total], [st.ms_vol_locate]
+    if args.full:
+        # per-stage device times of every step (HIP events): the same K steps
+        # again, each followed by a read of its event times (reported as means)
+        ms_vol, ms_tot, ms_walk = [], [], []
+        for _ in range(args.steps):
+            step()
+            st = ctx.sync()
+            ms_vol.append(st.ms_vol)
+            ms_tot.append(st.ms_total)
+            ms_walk.append(st.ms_vol_locate)
 
     npts = int(st.nvol + st.nbdy)
     agg = ranks.aggregate(ri, npts, elapsed, args.steps)
     gather = gathered = None
     if split:
-        gather, gathered = allgather_timing(ri, ctx, d_mo, d_fo, d_elem, d_hit, sh, counts, rank)
+        if args.full:
+            gather, gathered = allgather_timing(ri, ctx, d_mo, d_fo, d_elem, d_hit, sh, counts, rank)
         npts = agg["points_per_step"]  # the whole problem: bytes per point below are per problem point
     ms_per_step = agg["ms_per_step"]
     value = agg["mpts_per_s"]
@@ -958,6 +1034,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": round(ms_per_step, 4),
         "higher_is_better": True,
         # N = 1 is the first point of the default N > 1 curve (the same cfg4
@@ -982,6 +1059,7 @@ def main():
             "morton_binned": bool(st.sorted),
         },
         "gbps_algorithmic_step": round(B / (ms_per_step * 1e-3) / 1e9, 1),
+        # HIP events: means over the steps run again one by one (--full), else of the last timed step
         "device_ms": {"step_total": round(float(np.mean(ms_tot)), 4), "volume_stage": round(float(np.mean(ms_vol)), 4),
                       "volume_stage_last_timed_step": round(kvol_ms, 4),
                       "walk": round(float(np.mean(ms_walk)), 4),
@@ -1009,21 +1087,23 @@ def main():
             "algorithmic_bytes_per_point": round(per_pt, 2),
         },
     }
+    if dumped is not None:
+        out["outputs_dumped"] = dumped
     if gather is not None:
         out["allgather"] = gather
     if halo_info is not None:
         out["halo_shard"] = halo_info
-    if not args.no_host_mode and world == 1:
+    if args.full and not args.no_host_mode and world == 1:
         try:
             out["host_mode"] = host_mode_timing(ctx, w, bg, met, fields, q_xyz, q_pc, rank)
         except Exception as e:  # reported, never fatal to the bench line
             out["host_mode"] = {"error": str(e)}
-    if world == 1 and not split and not args.no_surface_solo:
+    if args.full and world == 1 and not split and not args.no_surface_solo:
         try:
             out["surface_solo"] = surface_solo(ctx, step_bg, d_qxyz, q_pc, d_mo, d_fo, d_elem, d_hit, local)
         except Exception as e:  # reported, never fatal to the bench line
             out["surface_solo"] = {"error": str(e)}
-    if not args.no_shuffled and world == 1 and not split:
+    if args.full and not args.no_shuffled and world == 1 and not split:
         legs = {"mmg_like_order": (synth.mmg_like_perm(nq), "the step on an Mmg-like numbering of the new points (1 in 6 "
                                    "points moved to the end as 'inserted', both parts in the generator's order); not "
                                    "the bench value"),
@@ -1048,26 +1128,26 @@ def main():
         except Exception as e:  # reported, never fatal to the bench line (e.g. a layout without packed records)
             out["shuffled_order_records"] = {"error": str(e)}
     gpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not split:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not split:
         # outputs of the last timed step (the host-mode call used its own buffers)
         gpu = {"elem": d_elem.download(), "hit": d_hit.download(), "met": d_mo.download(),
                "fields": [f.download() for f in d_fo]}
-    if not args.no_quality and not split:
+    if args.full and not args.no_quality and not split:
         try:
             out["tetra_qual"] = quality_timing(ctx, w, d_qxyz, d_mo, rank)
         except Exception as e:  # reported, never fatal to the bench line
             out["tetra_qual"] = {"error": str(e)}
-    if not args.no_snapshot and halo_info is None:  # (a shard's cut faces are no boundary trias)
+    if args.full and not args.no_snapshot and halo_info is None:  # (a shard's cut faces are no boundary trias)
         out["snapshot"] = snapshot_timing(ctx, bg, rank)
     ctx.close()
     # the groups leg after the large calls, in ParMmg's order (r05 ran it first: the lanes' streams then shared
     # hardware queues in some processes; r06: 3 lanes of 1 stream)
-    if not args.no_groups and world == 1 and not split:
+    if args.full and not args.no_groups and world == 1 and not split:
         try:
             out["groups"] = groups_leg(args)
         except Exception as e:  # reported, never fatal to the bench line
             out["groups"] = {"error": str(e)}
-    if not args.no_graded and world == 1 and not split and args.config == "cfg4":
+    if args.full and not args.no_graded and world == 1 and not split and args.config == "cfg4":
         try:
             out["graded"] = graded_leg(args, rank)
         except Exception as e:  # reported, never fatal to the bench line
@@ -1078,7 +1158,7 @@ def main():
         log(f"[bench r{rank}] parity of the GPU outputs against the oracle run")
         out["parity"] = parity_report(B_o, new, pclass, gpu, ref)
         log(f"[bench r{rank}] parity: {out['parity']}")
-    if split and rank == 0 and not args.no_cpu_baseline:
+    if args.full and split and rank == 0 and not args.no_cpu_baseline:
         log(f"[bench r{rank}] parity of the all-gathered results against an oracle run over the group")
         try:
             out["parity"] = split_parity(w, bg_group, met_group, fields_group, new, pclass, shards, gathered,

@@ -8,7 +8,7 @@ OUT=gpurun_out/${TAG:-run}
 mkdir -p $OUT
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ${PYTEST_ARGS} > $OUT/pytest_gpu.log 2>&1 \
 && echo "pytest ok" \
-&& timeout -k 10 600 python -u bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err \
+&& timeout -k 10 600 python -u bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err \
 && echo "bench ok" && cat $OUT/bench.json \
-&& timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 -u bench.py ${BENCH_ARGS} --no-cpu-baseline --no-host-mode --no-quality --no-snapshot --steps 5 --warmup 2 > $OUT/prof_bench.log 2>&1 \
+&& timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 -u bench.py --full ${BENCH_ARGS} --no-cpu-baseline --no-host-mode --no-quality --no-snapshot --steps 5 --warmup 2 > $OUT/prof_bench.log 2>&1 \
 && echo "rocprof ok"

@@ -10,7 +10,8 @@ goes to gpurun_out/<tag>/.  The driver process itself never touches the GPU
 Steps:
   pytest ARGS            python -m pytest ARGS -x -v --timeout 300 (thread method)
   sweep ARGS             tools/sweep.py ARGS (interleaved A/B of module settings)
-  bench ARGS             bench.py ARGS; the JSON line -> <tag>/bench[_N].json
+  bench ARGS             bench.py ARGS (--full among them for the side legs, the CPU
+                         baseline and the parity check); the JSON line -> <tag>/bench[_N].json
   pmcpy FILT CTRS ARGS   one rocprofv3 --pmc pass of python3 -u ARGS (a tools/ script), table of
                          the kernels matching FILT
   pmc CFG VARIANT CTRS   one rocprofv3 --pmc pass of tools/sweep.py (one live

@@ -10,7 +10,7 @@ i=0
 rc=0
 for set in "$@"; do
   i=$((i+1))
-  timeout -s KILL 120 rocprofv3 --pmc $set -d $OUT/p$i -o run --output-format csv -- python3 -u bench.py ${BENCH_ARGS} --no-cpu-baseline --steps 1 --warmup 1 > $OUT/p$i.log 2>&1 || { rc=$?; echo "pass $i failed rc=$rc"; break; }
+  timeout -s KILL 120 rocprofv3 --pmc $set -d $OUT/p$i -o run --output-format csv -- python3 -u bench.py --full ${BENCH_ARGS} --no-cpu-baseline --steps 1 --warmup 1 > $OUT/p$i.log 2>&1 || { rc=$?; echo "pass $i failed rc=$rc"; break; }
   echo "pass $i ok: $set"
 done
 exit $rc
