@@ -105,7 +105,9 @@ typedef struct {
   int64_t seed_map_axes; /* bit d: axis d of the volume seed grid followed the vertex quantiles */
   int64_t nbdy_fanscan;  /* surface queries whose cone test scanned every tria for a vertex's ball (its fan
                             open, non-manifold or longer than 64: e.g. at a halo shard's cut) */
-  int64_t reserved[6];   /* zero; room for later counters without changing the struct's size */
+  int64_t nvol_src;      /* volume queries whose walk began from the point map (pmmg_hip_set_point_map) */
+  int64_t nbdy_src;      /* surface queries whose tria walk began from the point map */
+  int64_t reserved[4];   /* zero; room for later counters without changing the struct's size */
 } pmmg_hip_stats;
 
 /* ABI of this header (r06): a shim built against it checks, once at load,
@@ -191,6 +193,42 @@ int pmmg_hip_locate_interp(pmmg_hip_ctx *ctx, int np_new, const double *xyz_new,
                            double *const *fields_out, int *elem_out,
                            int8_t *hit_out, pmmg_hip_stats *stats, int where);
 
+/* ---- Point map (Mmg's USE_POINTMAP) -------------------------------------------
+ * With USE_POINTMAP Mmg gives every new point the old-mesh vertex it descends
+ * from (MMG5_Point.src, src/libparmmg1.c:667-669); PMMG_locate_setStart
+ * (src/locate_pmmg.c:931-986) turns it into a start element per point — the
+ * first tria holding the source vertex for a boundary point, the first tetra
+ * for a volume point — and the walks begin there (src/interpmesh_pmmg.c:
+ * 552-554, 602-604) instead of at the previous point's element.
+ *
+ * Arms the next pmmg_hip_locate_interp / pmmg_hip_locate_interp_rec on this context:
+ * src[np_new], src[i] = 1-based background vertex the new point i+1 descends from
+ * (MMG5_Point.src under USE_POINTMAP), 0 = unknown.  Ids outside [1, np] of the
+ * background count as 0.  Consumed by that call; a call whose np_new differs
+ * returns 0 and disarms.  where = PMMG_HIP_HOST copies src (counted in bytes_up),
+ * PMMG_HIP_DEVICE records the pointer (must stay valid until the call completes).
+ *
+ * In the armed call a PMMG_PT_VOL point whose source has a start tetra begins
+ * its walk there, a PMMG_PT_BDY point whose source has a start tria begins
+ * its tria walk there (stats: nvol_src, nbdy_src); every other point — source
+ * unknown, or a surface point whose source is an interior vertex — takes the
+ * module's seed grids as in a call without a map, and a seed grid no query
+ * needs is not filled.  Results obey the same contract as without a map: the
+ * element of a point inside exactly one element does not depend on the start.
+ * pmmg_hip_locate_interp_groups neither consumes nor sees an armed map; the
+ * map refers to the background as set (an armed carry-over may coexist). */
+int pmmg_hip_set_point_map(pmmg_hip_ctx *ctx, int np_new, const int *src, int where);
+
+/* Downloads / copies the background's start tables (either may be NULL); builds them if needed.
+ * start_tet[np] / start_tri[np]: per background vertex the lowest-index in-use
+ * tetra (v[0] > 0) / boundary tria holding it, 0 when there is none — what
+ * PMMG_locate_setStart's ascending loops find.  The tables are built at the
+ * first armed call (or this call) on a background, on the device, after a
+ * device-built boundary is finished; they are kept until the next
+ * pmmg_hip_set_background* and freed by pmmg_hip_release_scratch (the next
+ * armed call builds them again). */
+int pmmg_hip_start_elements(pmmg_hip_ctx *ctx, int *start_tet, int *start_tri, int where);
+
 /* Wait for all work queued on the context (groups calls included); fills the
  * stats of the last PMMG_HIP_DEVICE pmmg_hip_locate_interp call.  Returns 1/0. */
 int pmmg_hip_sync(pmmg_hip_ctx *ctx, pmmg_hip_stats *stats);
@@ -229,7 +267,8 @@ int64_t pmmg_hip_bytes_up(pmmg_hip_ctx *ctx, int reset);
 
 /* Free the context's reusable scratch: the snapshot builders' buckets (12 B x
  * 4 x ne for the adjacency: ~4.8 GB at 101M tetra), the Morton binning's
- * second key / value arrays and digit tables, and the group lanes (contexts
+ * second key / value arrays and digit tables, the point map's start tables
+ * (pmmg_hip_start_elements), and the group lanes (contexts
  * of their own, re-created by the next groups call).  The next call that
  * needs any of them allocates it again.  Waits for the context's work first.
  * The background, solutions, kept slots and seed grids stay.  Returns 1/0. */

@@ -31,7 +31,7 @@ class HipStats(ctypes.Structure):
         ("ms_bdy", ctypes.c_float), ("ms_fallback", ctypes.c_float), ("ms_total", ctypes.c_float),
         ("ms_vol_locate", ctypes.c_float),
         ("nvol_noseed", c_int64), ("nvol_stuck", c_int64), ("nvol_limit", c_int64), ("seed_map_axes", c_int64),
-        ("nbdy_fanscan", c_int64), ("reserved", c_int64 * 6),
+        ("nbdy_fanscan", c_int64), ("nvol_src", c_int64), ("nbdy_src", c_int64), ("reserved", c_int64 * 4),
     ]
 
     def as_dict(self) -> dict:
@@ -63,6 +63,8 @@ HIP_API = {
     "pmmg_hip_set_solutions": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int]),
     "pmmg_hip_locate_interp": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, P(HipStats), c_int]),
+    "pmmg_hip_set_point_map": (c_int, [c_void_p, c_int, c_void_p, c_int]),
+    "pmmg_hip_start_elements": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "pmmg_hip_sync": (c_int, [c_void_p, P(HipStats)]),
     "pmmg_hip_locate_interp_groups": (c_int, [c_void_p, c_int, c_void_p, P(HipStats)]),
     "pmmg_hip_keep": (c_int, [c_void_p, c_int]),
@@ -144,6 +146,7 @@ HOST_API = {
     "pmmg_copy_metrics_and_fields_point": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),
     "pmmg_set_constant_metric": (c_int, [c_void_p]),
     "pmmg_interp_metrics_and_fields": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, P(HipStats)]),
+    "pmmg_interp_metrics_and_fields_map": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, P(HipStats)]),
     "pmmg_interp_metrics_and_fields_carry": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                                      P(HipStats)]),
     "pmmg_max_tet_extent": (c_double, [c_int, c_void_p, c_int, c_void_p]),

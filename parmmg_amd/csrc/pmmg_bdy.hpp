@@ -7,15 +7,17 @@
 
 namespace pmmg {
 
-// one surface query; returns the hit code (0 = not located: exhaustive list)
+// one surface query; returns the hit code (0 = not located: exhaustive list).
+// k0 != 0: the tria walk starts there (the point map's start tria,
+// src/interpmesh_pmmg.c:552-554) instead of at the seed grid's
 __device__ __forceinline__ int bdy_query(const Bg &bg, const Frame *fr, const unsigned long long *sgrid, int gs,
                                          const double *qxyz,
                                          int ip, const Slots &S, int *elem_out, int8_t *hit_out, int maxstep,
-                                         int &steps, int &scans, bool interp = true) {
+                                         int &steps, int &scans, int k0, bool interp = true) {
   int hit = 0;
   double x[3];
   load_pt(qxyz, ip, x);
-  int k = seed_srf(sgrid, gs, fr, x);
+  int k = k0 ? k0 : seed_srf(sgrid, gs, fr, x);
   if (k == 0) return 0;
   int hist[kHist];
 #pragma unroll
@@ -118,11 +120,14 @@ __device__ __forceinline__ int bdy_query(const Bg &bg, const Frame *fr, const un
 // slowed the volume kernel beside them (profiles/r03y).
 // (r05: a register budget for 5 or 6 waves per SIMD instead of the compiler's
 // 4: the step +-0 / +2 %, the 8-way rank's surface branch +-0, profiles/r05ak)
+// MAP = 1 (a call with a point map): a query whose source vertex has a start
+// tria begins there; a variant of its own, as k_vol's.
+template <int MAP = 0>
 __global__ __launch_bounds__(kBlock) void k_bdy(Bg bg, const Frame *fr, const unsigned long long *sgrid, int gs,
                                                 const double *qxyz,
                                                 const int *order, Slots S, int *elem_out, int8_t *hit_out, int *fb,
                                                 DevStats *st, int maxstep, int dyn, FbInit fi, FbGridBufs gb,
-                                                const int *gate, int want, unsigned long long *wt) {
+                                                const int *gate, int want, unsigned long long *wt, MapArgs ma) {
   if (want >= 0 && gate[0] != want) return; // (one of the two orders' launches, as k_vol)
 #ifdef PMMG_HIP_MEASURE
   // measurement build, PMMG_HIP_WAVETIME=1: per wave {start, end, longest walk, active lanes} (wall clock)
@@ -149,20 +154,22 @@ __global__ __launch_bounds__(kBlock) void k_bdy(Bg bg, const Frame *fr, const un
       i = ch.start + it * ch.stride;
     }
     const bool active = i < ((dyn & 1) ? hi : ch.hi);
-    int steps = 0, hit = 0, ip = 0, scans = 0;
+    int steps = 0, hit = 0, ip = 0, scans = 0, k0 = 0;
     if (active) {
       ip = order[i];
+      if constexpr (MAP != 0) k0 = map_start(ma.src, ma.start_tri, bg.np, bg.nt, ip, false);
       // (measurement build, dyn bit 1 = PMMG_HIP_BDYNOINTERP=1: the walks without the interpolation; r06w:
       // the interpolation is ~half of a surface wave's lifetime.  r06x: a cooperative version — the three
       // vertices' rows gathered by the wave through LDS, 8-byte pieces — made the waves longer, 32 vs 30 us,
       // and the step +27 us: not kept)
 #ifdef PMMG_HIP_MEASURE
-      hit = bdy_query(bg, fr, sgrid, gs, qxyz, ip, S, elem_out, hit_out, maxstep, steps, scans, !(dyn & 2));
+      hit = bdy_query(bg, fr, sgrid, gs, qxyz, ip, S, elem_out, hit_out, maxstep, steps, scans, k0, !(dyn & 2));
 #else
-      hit = bdy_query(bg, fr, sgrid, gs, qxyz, ip, S, elem_out, hit_out, maxstep, steps, scans);
+      hit = bdy_query(bg, fr, sgrid, gs, qxyz, ip, S, elem_out, hit_out, maxstep, steps, scans, k0);
 #endif
     }
     wave_count(&bs, kCntFanScan, active && scans > 0);
+    if constexpr (MAP != 0) wave_count(&bs, kCntBdySrc, active && k0 != 0);
     int slot = wave_append(&st->nfb_bdy, active && hit == 0);
     if (active && hit == 0) {
       fb[slot] = ip;

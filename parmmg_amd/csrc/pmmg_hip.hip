@@ -9,6 +9,8 @@
 //   PMMG_locatePointBdy      src/locate_pmmg.c:587-723     -> k_bdy (locate + interpolate)  (pmmg_bdy.hpp)
 //   exhaustive / closest     src/locate_pmmg.c:477-515, 737-770 -> k_*_exhaust_accept, k_*_exhaust_closest
 //                                                             (pmmg_fallback.hpp)
+//   PMMG_locate_setStart     src/locate_pmmg.c:931-986     -> k_start_tet / k_start_tri and the MAP variants of
+//                                                             k_vol / k_bdy (USE_POINTMAP; pmmg_prep.hpp)
 // Device arithmetic: pmmg_device.hpp; preparation and query order:
 // pmmg_prep.hpp.
 //
@@ -62,24 +64,26 @@ namespace {
 
 typedef void (*VolFn)(Bg, const Frame *, const unsigned long long *, int, const double *, const uint8_t *,
                       const int *, const double *, int, ContEntry *, DevStats *, Slots, int *, int8_t *, int,
-                      const int *, int, int, int, LocBuf, int, ContArgs);
+                      const int *, int, int, int, LocBuf, int, ContArgs, MapArgs);
 typedef void (*InterpFn)(LocBuf, const int *, const DevStats *, int, Slots, const int *, int, int, int);
 
 // the split stage's walk kernel: the locate-only layout, writing located records
 constexpr VolFn kVolWalk = k_vol<0, 0, 0, 0, 0, 0, 0>;
+constexpr VolFn kVolWalkMap = k_vol<0, 0, 0, 0, 0, 0, 0, 1>; // (a call with a point map)
 
 struct LayoutEntry {
   int c[6];
   VolFn fn;         // one array per solution (the reference's layout)
   VolFn fn_packed;  // packed per-vertex records, one pass (null: layout not packable)
   VolFn fn_packed2; // the same in two passes over the record halves (null: not splittable)
+  VolFn map_fn, map_fn_packed, map_fn_packed2; // the same three for a call with a point map (k_vol's MAP)
   InterpFn ifn, ifn_packed, ifn_packed2; // the split stage's interpolation kernels, same three forms
 };
 
-template <int NP, int A, int B, int C, int D, int E, int F>
+template <int NP, int A, int B, int C, int D, int E, int F, int MAP = 0>
 constexpr VolFn packed_fn() {
   using L = PackedLayout<A, B, C, D, E, F>;
-  if constexpr (L::valid() && L::passes_ok(NP)) return k_vol<NP, A, B, C, D, E, F>;
+  if constexpr (L::valid() && L::passes_ok(NP)) return k_vol<NP, A, B, C, D, E, F, MAP>;
   else return nullptr;
 }
 template <int NP, int A, int B, int C, int D, int E, int F>
@@ -91,7 +95,8 @@ constexpr InterpFn packed_ifn() {
 
 #define PMMG_LAYOUT(a, b, c, d, e, f)                                                                    \
   {{a, b, c, d, e, f}, k_vol<0, a, b, c, d, e, f>, packed_fn<1, a, b, c, d, e, f>(),                    \
-   packed_fn<2, a, b, c, d, e, f>(), k_vol_interp<0, a, b, c, d, e, f>, packed_ifn<1, a, b, c, d, e, f>(), \
+   packed_fn<2, a, b, c, d, e, f>(), k_vol<0, a, b, c, d, e, f, 1>, packed_fn<1, a, b, c, d, e, f, 1>(), \
+   packed_fn<2, a, b, c, d, e, f, 1>(), k_vol_interp<0, a, b, c, d, e, f>, packed_ifn<1, a, b, c, d, e, f>(), \
    packed_ifn<2, a, b, c, d, e, f>()}
 // common slot layouts (metric first): aniso metric + scalar/vector/tensor
 // (BASELINE cfg3/cfg4, libexamples cube-solphys.sol), iso metric + scalars
@@ -112,7 +117,7 @@ struct VolPick {
   VolFn fn;     // the fused kernel (walk + exact test + interpolation)
   InterpFn ifn; // the split stage's interpolation kernel (after kVolWalk)
 };
-VolPick pick_layout(const Slots &S, int passes = 0) {
+VolPick pick_layout(const Slots &S, int passes = 0, bool map = false) {
   for (const LayoutEntry &e : kLayouts) {
     int n = 0;
     while (n < 6 && e.c[n] > 0) n++;
@@ -120,18 +125,19 @@ VolPick pick_layout(const Slots &S, int passes = 0) {
     bool ok = true;
     for (int j = 0; j < n; j++) ok = ok && (S.s[j].code == e.c[j]);
     if (!ok) continue;
-    if (!S.rec) return {e.fn, e.ifn};
+    if (!S.rec) return {map ? e.map_fn : e.fn, e.ifn};
     if (passes == 0) {
       int k = 0;
       for (int j = 0; j < n; j++) k += e.c[j];
       passes = k > 8 ? 2 : 1;
     }
-    VolFn a = passes == 2 ? e.fn_packed2 : e.fn_packed, b = passes == 2 ? e.fn_packed : e.fn_packed2;
+    const VolFn p1 = map ? e.map_fn_packed : e.fn_packed, p2 = map ? e.map_fn_packed2 : e.fn_packed2;
+    VolFn a = passes == 2 ? p2 : p1, b = passes == 2 ? p1 : p2;
     InterpFn ia = passes == 2 ? e.ifn_packed2 : e.ifn_packed, ib = passes == 2 ? e.ifn_packed : e.ifn_packed2;
     return {a ? a : b, ia ? ia : ib};
   }
   if (S.rec) return {nullptr, nullptr};
-  return {k_vol<0, -1, 0, 0, 0, 0, 0>, k_vol_interp<0, -1, 0, 0, 0, 0, 0>};
+  return {map ? k_vol<0, -1, 0, 0, 0, 0, 0, 1> : k_vol<0, -1, 0, 0, 0, 0, 0>, k_vol_interp<0, -1, 0, 0, 0, 0, 0>};
 }
 
 
@@ -295,6 +301,16 @@ struct pmmg_hip_ctx {
   std::vector<int> carry_src;  // next vertex i+1 = kept point carry_src[i] (0: host row); empty: identity
   DevBuf carry_dsrc, carry_need, carry_ids, carry_cnt, carry_rows, carry_bc;
   int64_t bytes_up = 0; // host -> device bytes of host-mode calls (pmmg_hip_bytes_up)
+  // point map (pmmg_hip_set_point_map): map_src != null arms the next locate_interp(_rec) of map_np new
+  // points, which consumes it.  start_tab: the background's start tables, start_tet[np] then start_tri[np]
+  // (k_start_tet / k_start_tri), built at the first mapped call or pmmg_hip_start_elements on a background
+  // and kept until the next set_background* or pmmg_hip_release_scratch
+  const int *map_src = nullptr;
+  int map_np = 0;
+  DevBuf map_own;  // the copy of a PMMG_HIP_HOST map
+  DevBuf map_need; // the call's volume / surface queries without a mapped start (k_map_count)
+  DevBuf start_tab;
+  bool start_valid = false;
   // pmmg_hip_locate_interp_groups: lanes[j] is lane j (same device and
   // options, created at the first groups call); lane 0 enqueues on this
   // context's own streams (no extra hardware queue) but has its own state, so
@@ -631,6 +647,7 @@ static void invalidate_bg(pmmg_hip_ctx *c) {
   c->bg.tetv = c->bg.adja = nullptr;
   c->bg.triv = c->bg.adjt = nullptr;
   c->bg.xyz = nullptr;
+  c->start_valid = false;
 }
 
 // wait for a deferred device snapshot (host-mode set_background); 0 if it failed
@@ -821,7 +838,7 @@ void pmmg_hip_destroy(pmmg_hip_ctx *c) {
                     &c->fbg_vol_u, &c->fbg_vol_i, &c->fbg_bdy_c, &c->fbg_bdy_u, &c->fbg_bdy_i, &c->h_xyz,
                     &c->h_cls, &c->h_met, &c->h_elem, &c->h_hit, &c->brk_k, &c->brk_k2, &c->brk_v, &c->brk_v2,
                     &c->brk_vinv, &c->brk_tinv, &c->brk_xq, &c->brk_xyz, &c->brk_sol, &c->brk_rec, &c->brk_tmp,
-                    &c->locv, &c->locp, &c->wt};
+                    &c->locv, &c->locp, &c->wt, &c->map_own, &c->map_need, &c->start_tab};
   for (DevBuf *b : bufs) release(*b);
   for (auto &b : c->o_f) release(b);
   for (auto &b : c->h_f) release(b);
@@ -1057,6 +1074,7 @@ static int set_background_impl(pmmg_hip_ctx *c, int np, const double *xyz, int n
   if (!c) return 0;
   HIPCK(c, hipSetDevice(c->device));
   if (!snap_join(c)) return 0;
+  c->start_valid = false; // (the start tables belong to the background they were built on)
   const bool packed = tet8 != nullptr;
   const bool build_bdy = nt < 0 && !triv;
   if (np <= 0 || ne <= 0 || !xyz || (!packed && !tetv) || (nt < 0 && triv) || (nt > 0 && !triv)) {
@@ -1441,13 +1459,32 @@ static int brick_renumber(pmmg_hip_ctx *c, hipStream_t s, const Bg &bg, const Sl
 }
 #endif
 
+// The background's start tables (pmmg_prep.hpp: point map), built on the
+// main stream when the background has none yet: start_tet[np], start_tri[np].
+static int start_tables(pmmg_hip_ctx *c) {
+  if (c->start_valid) return 1;
+  const Bg &bg = c->bg;
+  const size_t n = 2 * (size_t)bg.np;
+  if (!ensure(c, c->start_tab, sizeof(int) * n)) return 0;
+  unsigned *tab = (unsigned *)c->start_tab.p;
+  HIPCK(c, hipMemsetAsync(tab, 0xFF, sizeof(int) * n, c->stream));
+  hipLaunchKernelGGL(k_start_tet, dim3(blocks_for(bg.ne, 16384)), dim3(kBlock), 0, c->stream, bg, tab);
+  if (bg.nt > 0)
+    hipLaunchKernelGGL(k_start_tri, dim3(blocks_for(bg.nt, 4096)), dim3(kBlock), 0, c->stream, bg, tab + bg.np);
+  hipLaunchKernelGGL(k_start_fin, dim3(blocks_for((long long)n, 4096)), dim3(kBlock), 0, c->stream, tab, (long long)n);
+  HIPCK(c, hipGetLastError());
+  c->start_valid = true;
+  return 1;
+}
+
 // The pipeline of one call on device pointers.  It enqueues its kernels on
 // the context's two streams and reads nothing back: in auto order mode both
 // the Morton binning and the input-order compaction are enqueued, each gated
 // on the coherence test's flag on the device (r04), and every fallback kernel
 // reads its list's count on the device.
 static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const uint8_t *pclass, double *met_out,
-                      double *const *fields_out, int *elem_out, int8_t *hit_out, double *rec_out = nullptr) {
+                      double *const *fields_out, int *elem_out, int8_t *hit_out, double *rec_out = nullptr,
+                      const int *map_src = nullptr) {
   Bg bg = c->bg;
   hipStream_t s = c->stream, sb = c->stream2;
   // Measurement build (PMMG_HIP_SRFPRIO=1): a large call runs its second
@@ -1503,7 +1540,7 @@ static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const 
     }
     S.rec_out = rec_out;
   }
-  const VolPick vpick = pick_layout(S, c->pack_passes);
+  const VolPick vpick = pick_layout(S, c->pack_passes, map_src != nullptr);
   if (!vpick.fn) {
     set_err(c, "locate_interp: no packed-record kernel for this slot layout");
     return 0;
@@ -1519,7 +1556,16 @@ static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const 
         if (!e) HIPCK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     if (!c->ev_interp) HIPCK(c, hipEventCreateWithFlags(&c->ev_interp, hipEventDisableTiming));
   }
-  const VolFn vol_fn = vsplit ? kVolWalk : vpick.fn;
+  const VolFn vol_fn = vsplit ? (map_src ? kVolWalkMap : kVolWalk) : vpick.fn;
+  // a call with a point map: the background's start tables (built now if it has none), and the counts of
+  // queries the map gives no start, which gate the seed grids on the device
+  MapArgs ma{nullptr, nullptr, nullptr};
+  int *need = nullptr;
+  if (map_src) {
+    if (!start_tables(c) || !ensure(c, c->map_need, 2 * sizeof(int))) return 0;
+    need = (int *)c->map_need.p;
+    ma = MapArgs{map_src, (const int *)c->start_tab.p, (const int *)c->start_tab.p + bg.np};
+  }
   const int g = grid_dim(bg.ne, c->tpc, 1024);
   const int gs = bg.nt <= 0 ? 1 : (c->srf_g > 0 ? c->srf_g : grid_dim((long long)bg.nt * c->srf_mult, 2, 1024));
   const int gb = 1 << kBinBitsAxis;
@@ -1584,6 +1630,11 @@ static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const 
   hipExtLaunchKernelGGL(k_reset, dim3(blocks_for(ng_clr > nsg_clr ? ng_clr : nsg_clr, 2048)), dim3(kBlock), 0, s,
                         c->ev[EV_START], force >= 0 ? c->ev[EV_RESET] : nullptr, 0, fr, st, grid, ng_clr, sgrid,
                         nsg_clr, (int *)c->oflag.p, force, c->bin_bits);
+  if (map_src) {
+    HIPCK(c, hipMemsetAsync(need, 0, 2 * sizeof(int), s));
+    hipLaunchKernelGGL(k_map_count, dim3(blocks_for(np_new, 2048)), dim3(kBlock), 0, s, pclass, (long long)np_new, ma,
+                       bg.np, bg.ne, bg.nt, need);
+  }
   // bbox (its last block finalises the frame), the seed grid's axis maps
   // (auto order: the queries' coherence test rides along, its flag read by the order and volume kernels)
   // the second stream needs the frame only (lo, inv_bin, inv_srf), not the
@@ -1645,7 +1696,8 @@ static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const 
     // took 107 us — the grid's latency in rounds of waves — where cfg4's 12.6M take 262 us)
     hipExtLaunchKernelGGL(k_seed_vol, dim3((blocks_for((nsamp + kSeedBatch - 1) / kSeedBatch, 8192) + 7) & ~7),
                           dim3(kBlock), 0, s, nullptr, quant_side ? nullptr : c->ev[EV_PREP], 0, bg, fr, grid, g,
-                          nsamp, c->seed_lanes, c->seed_v0, quant_side ? bg.xyz : (const double *)nullptr);
+                          nsamp, c->seed_lanes, c->seed_v0, quant_side ? bg.xyz : (const double *)nullptr,
+                          (const int *)need);
     if (quant_side) { // (the walk reads the fixed-point copy)
       HIPCK(c, hipStreamWaitEvent(s, c->ev[EV_QUANT], 0));
       HIPCK(c, hipEventRecord(c->ev[EV_PREP], s));
@@ -1723,12 +1775,13 @@ static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const 
   // k_bdy's blocks: kBlock threads, or one wave each (bdy_wave), so that they fit into the single-wave
   // slots the volume kernel's one-wave blocks leave while it runs beside them
   const int bdy_tpb = c->bdy_wave ? 64 : kBlock;
+  const auto bdy_fn = map_src ? k_bdy<1> : k_bdy<0>;
   auto bdy = [&](int want) {
-    hipLaunchKernelGGL(k_bdy, dim3(8 * blocks_for((np_new + 7) / 8, c->bdy_bpx) * (kBlock / bdy_tpb)), dim3(bdy_tpb),
+    hipLaunchKernelGGL(bdy_fn, dim3(8 * blocks_for((np_new + 7) / 8, c->bdy_bpx) * (kBlock / bdy_tpb)), dim3(bdy_tpb),
                        0, sb, bg,
                        (const Frame *)fr, (const unsigned long long *)sgrid, gs, xyz_new, (const int *)order_b, S, elem_out,
                        hit_out, (int *)c->fb_bdy.p, st, c->maxstep, c->bdy_dyn, FbInit{(int *)c->bbest.p},
-                       FbGridBufs{(int *)c->fbg_bdy_c.p, (int *)c->fbg_bdy_u.p, (int *)c->fbg_bdy_i.p}, flag, want, wt);
+                       FbGridBufs{(int *)c->fbg_bdy_c.p, (int *)c->fbg_bdy_u.p, (int *)c->fbg_bdy_i.p}, flag, want, wt, ma);
   };
   // ---- surface branch (second stream, after the order): seeds, k_bdy
   // (r05ae: the surface seeds moved before the wait for the volume seed grid, beside it: preparation
@@ -1740,7 +1793,8 @@ static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const 
     if (bg.nt > 0) {
       if (force == 0) HIPCK(c, hipStreamWaitEvent(sb, c->ev[EV_FRAME], 0)); // (the surface seeds need the frame)
       hipExtLaunchKernelGGL(k_seed_srf, dim3(blocks_for(bg.nt, 4096) * (kBlock / bdy_tpb)), dim3(bdy_tpb), 0, sb,
-                            c->ev[EV_BDY0], nullptr, 0, bg, (const Frame *)fr, sgrid, gs);
+                            c->ev[EV_BDY0], nullptr, 0, bg, (const Frame *)fr, sgrid, gs,
+                            need ? (const int *)need + 1 : (const int *)nullptr);
       if (c->vol_wait_seed) HIPCK(c, hipEventRecord(c->ev[EV_SRFSEED], sb));
     }
     return 1;
@@ -1784,7 +1838,7 @@ static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const 
       hipExtLaunchKernelGGL(vol_fn, dim3(nb), dim3(64), 0, s, nullptr, stop, 0, bg, (const Frame *)fr,
                             (const unsigned long long *)grid, g, xyz_new, pclass, (const int *)order_v,
                             c->bin_qs ? (const double *)c->qs.p : nullptr, np_new, (ContEntry *)c->cont.p, st, S,
-                            elem_out, hit_out, c->filter_steps, flag, c->xcd_run, c->pad, want, lb, 0, ca);
+                            elem_out, hit_out, c->filter_steps, flag, c->xcd_run, c->pad, want, lb, 0, ca, ma);
       return;
     }
     // split stage: walk chunk j (main stream), then its interpolation on stream_i, beside walk chunk j + 1
@@ -1798,7 +1852,7 @@ static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const 
       hipLaunchKernelGGL(vol_fn, dim3(nbj), dim3(64), 0, s, bg, (const Frame *)fr, (const unsigned long long *)grid,
                          g, xyz_new, pclass, (const int *)order_v, c->bin_qs ? (const double *)c->qs.p : nullptr,
                          np_new, (ContEntry *)c->cont.p, st, S, elem_out, hit_out, c->filter_steps, flag,
-                         c->xcd_run, c->pad, want, lb, b0, ca);
+                         c->xcd_run, c->pad, want, lb, b0, ca, ma);
       hipEvent_t ej = c->ev_chunk[w][std::min(j, (int)pmmg_hip_ctx::kMaxVolChunks - 1)];
       (void)hipEventRecord(ej, s);
       (void)hipStreamWaitEvent(c->stream_i, ej, 0);
@@ -1989,6 +2043,8 @@ static int collect_stats(pmmg_hip_ctx *c, pmmg_hip_stats *out) {
     HIPCK(c, ctx_d2h(c, &ad, &((const Frame *)c->frame.p)->adaptive, sizeof(int)));
     out->seed_map_axes = ad;
     out->nbdy_fanscan = (int64_t)cnt[kCntFanScan];
+    out->nvol_src = (int64_t)cnt[kCntVolSrc];
+    out->nbdy_src = (int64_t)cnt[kCntBdySrc];
   }
   float ms = 0.f;
   HIPCK(c, hipEventElapsedTime(&ms, c->ev[EV_START], c->ev[EV_PREP]));
@@ -2022,10 +2078,61 @@ int pmmg_hip_sync(pmmg_hip_ctx *c, pmmg_hip_stats *stats) {
   return 1;
 }
 
+// The armed point map, taken by a locate_interp(_rec) call whatever becomes
+// of the call; 0 (with the map dropped) when it was armed for another np_new.
+static int take_point_map(pmmg_hip_ctx *c, int np_new, const int **src) {
+  *src = c->map_src;
+  c->map_src = nullptr;
+  if (*src && c->map_np != np_new) {
+    set_err(c, "locate_interp: the point map was armed for %d new points, the call has %d", c->map_np, np_new);
+    return 0;
+  }
+  return 1;
+}
+
+int pmmg_hip_set_point_map(pmmg_hip_ctx *c, int np_new, const int *src, int where) {
+  if (!c) return 0;
+  c->map_src = nullptr;
+  if (np_new <= 0 || !src) {
+    set_err(c, "set_point_map: np_new = %d or src NULL", np_new);
+    return 0;
+  }
+  if (where == PMMG_HIP_DEVICE) {
+    c->map_src = src;
+  } else {
+    HIPCK(c, hipSetDevice(c->device));
+    if (!snap_join(c)) return 0;
+    if (!upload(c, c->map_own, src, sizeof(int) * (size_t)np_new)) return 0;
+    c->map_src = (const int *)c->map_own.p;
+  }
+  c->map_np = np_new;
+  return 1;
+}
+
+int pmmg_hip_start_elements(pmmg_hip_ctx *c, int *start_tet, int *start_tri, int where) {
+  if (!c) return 0;
+  HIPCK(c, hipSetDevice(c->device));
+  if (!snap_join(c)) return 0;
+  if (c->bg.ne <= 0) {
+    set_err(c, "start_elements: no background set");
+    return 0;
+  }
+  if (!start_tables(c)) return 0;
+  const size_t bytes = sizeof(int) * (size_t)c->bg.np;
+  const int *tab = (const int *)c->start_tab.p;
+  const hipMemcpyKind kind = where == PMMG_HIP_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (start_tet) HIPCK(c, hipMemcpyAsync(start_tet, tab, bytes, kind, c->stream));
+  if (start_tri) HIPCK(c, hipMemcpyAsync(start_tri, tab + c->bg.np, bytes, kind, c->stream));
+  HIPCK(c, hipStreamSynchronize(c->stream));
+  return 1;
+}
+
 int pmmg_hip_locate_interp(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const uint8_t *pclass,
                            double *met_out, double *const *fields_out, int *elem_out, int8_t *hit_out,
                            pmmg_hip_stats *stats, int where) {
   if (!c) return 0;
+  const int *map_src = nullptr;
+  if (!take_point_map(c, np_new, &map_src)) return 0;
   HIPCK(c, hipSetDevice(c->device));
   if (!snap_join(c)) return 0;
   if (c->bg.ne <= 0) {
@@ -2045,7 +2152,7 @@ int pmmg_hip_locate_interp(pmmg_hip_ctx *c, int np_new, const double *xyz_new, c
       set_err(c, "locate_interp: a device tensor output must be 16-byte aligned");
       return 0;
     }
-    if (!run_device(c, np_new, xyz_new, pclass, met_out, fields_out, elem_out, hit_out)) return 0;
+    if (!run_device(c, np_new, xyz_new, pclass, met_out, fields_out, elem_out, hit_out, nullptr, map_src)) return 0;
     if (stats) return pmmg_hip_sync(c, stats);
     return 1;
   }
@@ -2085,7 +2192,7 @@ int pmmg_hip_locate_interp(pmmg_hip_ctx *c, int np_new, const double *xyz_new, c
   if (!ensure(c, c->h_elem, sizeof(int) * n) || !ensure(c, c->h_hit, n)) return 0;
   HIPCK(c, hipMemsetAsync(c->h_hit.p, 0, n, c->stream));
   if (!run_device(c, np_new, (const double *)c->h_xyz.p, (const uint8_t *)c->h_cls.p, dmet, dfields.data(),
-                  (int *)c->h_elem.p, (int8_t *)c->h_hit.p))
+                  (int *)c->h_elem.p, (int8_t *)c->h_hit.p, nullptr, map_src))
     return 0;
   const double t1 = now_s();
   std::vector<int8_t> hh(n);
@@ -2119,6 +2226,8 @@ int pmmg_hip_locate_interp(pmmg_hip_ctx *c, int np_new, const double *xyz_new, c
 int pmmg_hip_locate_interp_rec(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const uint8_t *pclass,
                                double *rec_out, int *elem_out, int8_t *hit_out, pmmg_hip_stats *stats, int where) {
   if (!c) return 0;
+  const int *map_src = nullptr;
+  if (!take_point_map(c, np_new, &map_src)) return 0;
   HIPCK(c, hipSetDevice(c->device));
   if (!snap_join(c)) return 0;
   if (where != PMMG_HIP_DEVICE) {
@@ -2141,7 +2250,7 @@ int pmmg_hip_locate_interp_rec(pmmg_hip_ctx *c, int np_new, const double *xyz_ne
     set_err(c, "locate_interp_rec: xyz_new / pclass / rec_out NULL or rec_out not 16-byte aligned");
     return 0;
   }
-  if (!run_device(c, np_new, xyz_new, pclass, nullptr, nullptr, elem_out, hit_out, rec_out)) return 0;
+  if (!run_device(c, np_new, xyz_new, pclass, nullptr, nullptr, elem_out, hit_out, rec_out, map_src)) return 0;
   if (stats) return pmmg_hip_sync(c, stats);
   return 1;
 }
@@ -2225,7 +2334,8 @@ int pmmg_hip_release_scratch(pmmg_hip_ctx *c) {
   HIPCK(c, hipStreamSynchronize(c->stream2));
   if (c->stream3) HIPCK(c, hipStreamSynchronize(c->stream3));
   pmmg_snap_cache_free(&c->snap_cache);
-  for (DevBuf *b : {&c->bvals2, &c->rs_hist, &c->rs_csum}) release(*b);
+  for (DevBuf *b : {&c->bvals2, &c->rs_hist, &c->rs_csum, &c->start_tab}) release(*b);
+  c->start_valid = false; // (the next call with a point map builds the start tables again)
   for (pmmg_hip_ctx *l : c->lanes) pmmg_hip_destroy(l);
   c->lanes.clear();
   return 1;
@@ -2255,6 +2365,7 @@ static void stats_sum(pmmg_hip_stats *a, const pmmg_hip_stats &b) {
   a->nvol_noseed += b.nvol_noseed; a->nvol_stuck += b.nvol_stuck; a->nvol_limit += b.nvol_limit;
   a->seed_map_axes |= b.seed_map_axes;
   a->nbdy_fanscan += b.nbdy_fanscan;
+  a->nvol_src += b.nvol_src; a->nbdy_src += b.nbdy_src;
 }
 
 static pmmg_hip_ctx *group_lane(pmmg_hip_ctx *c, int j) {

@@ -165,10 +165,12 @@ static void stats_add(pmmg_hip_stats *a, const pmmg_hip_stats *b) {
   a->nvol_noseed += b->nvol_noseed; a->nvol_stuck += b->nvol_stuck; a->nvol_limit += b->nvol_limit;
   a->seed_map_axes |= b->seed_map_axes;
   a->nbdy_fanscan += b->nbdy_fanscan;
+  a->nvol_src += b->nvol_src; a->nbdy_src += b->nbdy_src;
 }
 
 static int interp_groups(pmmg_hip_ctx *ctx, int ngrp, const pmmg_old_group *old, pmmg_new_group *grp, int input_met,
-                         int keep, int carried, const int *const *src, pmmg_hip_stats *stats) {
+                         int keep, int carried, const int *const *src, const int *const *pmap,
+                         pmmg_hip_stats *stats) {
   if (!ctx) {
     fprintf(stderr, "[parmmg_host] no HIP context: the transfer step has no CPU fallback\n");
     return 0;
@@ -215,6 +217,8 @@ static int interp_groups(pmmg_hip_ctx *ctx, int ngrp, const pmmg_old_group *old,
                                      o->hausd, PMMG_HIP_HOST) &&
              pmmg_hip_set_solutions(ctx, ismet ? o->met_size : 0, ismet ? o->met : NULL, o->nfield,
                                     o->field_size, o->field, PMMG_HIP_HOST);
+    /* USE_POINTMAP: the group's MMG5_Point.src arms the call (pmmg_hip_set_point_map) */
+    if (ok && pmap && pmap[ig]) ok = pmmg_hip_set_point_map(ctx, g->np, pmap[ig], PMMG_HIP_HOST);
     pmmg_hip_stats st;
     if (ok)
       ok = pmmg_hip_locate_interp(ctx, g->np, g->xyz, pclass, ismet ? g->met : NULL, g->field, g->elem, g->hit,
@@ -230,11 +234,17 @@ static int interp_groups(pmmg_hip_ctx *ctx, int ngrp, const pmmg_old_group *old,
 
 int pmmg_interp_metrics_and_fields(pmmg_hip_ctx *ctx, int ngrp, const pmmg_old_group *old, pmmg_new_group *grp,
                                    int input_met, pmmg_hip_stats *stats) {
-  return interp_groups(ctx, ngrp, old, grp, input_met, 0, 0, NULL, stats);
+  return interp_groups(ctx, ngrp, old, grp, input_met, 0, 0, NULL, NULL, stats);
+}
+
+int pmmg_interp_metrics_and_fields_map(pmmg_hip_ctx *ctx, int ngrp, const pmmg_old_group *old, pmmg_new_group *grp,
+                                       int input_met, const int *const *src, pmmg_hip_stats *stats) {
+  if (!ctx || !old || !grp) return 0;
+  return interp_groups(ctx, ngrp, old, grp, input_met, 0, 0, NULL, src, stats);
 }
 
 int pmmg_interp_metrics_and_fields_carry(pmmg_hip_ctx *ctx, int ngrp, const pmmg_old_group *old,
                                          pmmg_new_group *grp, int input_met, int carried, const int *const *src,
                                          pmmg_hip_stats *stats) {
-  return interp_groups(ctx, ngrp, old, grp, input_met, 1, carried, src, stats);
+  return interp_groups(ctx, ngrp, old, grp, input_met, 1, carried, src, NULL, stats);
 }

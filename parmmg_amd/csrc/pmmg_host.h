@@ -107,6 +107,16 @@ int pmmg_interp_metrics_and_fields_carry(pmmg_hip_ctx *ctx, int ngrp, const pmmg
                                          pmmg_new_group *grp, int input_met, int carried, const int *const *src,
                                          pmmg_hip_stats *stats);
 
+/* pmmg_interp_metrics_and_fields with Mmg's point map (USE_POINTMAP): src[ig]
+ * = group ig's MMG5_Point.src packed per new point (src[ig][i] = 1-based
+ * vertex of old group ig that new point i+1 descends from, 0 = unknown),
+ * handed to pmmg_hip_set_point_map before the group's transfer, so that its
+ * walks start where PMMG_locate_setStart (src/locate_pmmg.c:931-986) would
+ * start them.  src NULL or src[ig] NULL: that group runs without a map.
+ * Returns 0 without touching anything when ctx, old or grp is NULL. */
+int pmmg_interp_metrics_and_fields_map(pmmg_hip_ctx *ctx, int ngrp, const pmmg_old_group *old, pmmg_new_group *grp,
+                                       int input_met, const int *const *src, pmmg_hip_stats *stats);
+
 /* ---- halo shards of a background group (pmmg_shard.c) ----
  * All arrays in the "row r = entity r+1" layout of parmmg_hip.h. */
 

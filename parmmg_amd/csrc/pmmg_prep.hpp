@@ -53,6 +53,8 @@ constexpr int kCntNoSeed = 15;     // volume queries without a seed (empty seed 
 constexpr int kCntStuck = 16;      // exact walks stuck (no eligible neighbour)
 constexpr int kCntLimit = 17;      // exact walks stopped at maxstep
 constexpr int kCntFanScan = 18;    // surface queries whose cone test scanned every tria (tri_cone_scan)
+constexpr int kCntVolSrc = 19;     // volume queries whose walk began from the point map (pmmg_hip_set_point_map)
+constexpr int kCntBdySrc = 0;      // surface queries likewise (the slot of PMMG_HIT_NONE, which is never counted)
 constexpr int kNumCnt = 20;
 struct StatPart {
   unsigned long long cnt[kNumCnt];
@@ -456,8 +458,12 @@ constexpr unsigned long long kSeedIdMask = (1ULL << 29) - 1; // ids below 2^29 (
 // axis (the uniform map folded with the fixed-point frame); an axis with a
 // quantile map (Frame::adaptive) goes through seed_pos.
 constexpr int kSeedBatch = 3;
+// need != null (a call with a point map): the count of volume queries the map
+// gives no start (k_map_count); the grid is not filled when it is zero.
 __global__ __launch_bounds__(kBlock) void k_seed_vol(Bg bg, Frame *fr, unsigned long long *cell, int g,
-                                                     long long nsamp, int lanes, int v0only, const double *xyzc) {
+                                                     long long nsamp, int lanes, int v0only, const double *xyzc,
+                                                     const int *need) {
+  if (need && *need == 0) return;
   constexpr int R = kSeedRun, B = kSeedBatch;
   __shared__ int smin;
   if (threadIdx.x == 0) smin = INT_MAX;
@@ -695,7 +701,10 @@ __device__ __forceinline__ unsigned long long srf_key(const double *p, const Fra
   return ((unsigned long long)q8 << 56) | (off << 29);
 }
 
-__global__ __launch_bounds__(kBlock) void k_seed_srf(Bg bg, const Frame *fr, unsigned long long *cell, int g) {
+// (need: as k_seed_vol's, the count of surface queries without a mapped start)
+__global__ __launch_bounds__(kBlock) void k_seed_srf(Bg bg, const Frame *fr, unsigned long long *cell, int g,
+                                                     const int *need) {
+  if (need && *need == 0) return;
   for (int k = 1 + blockIdx.x * blockDim.x + threadIdx.x; k <= bg.nt; k += gridDim.x * blockDim.x) {
     const int *tv = bg.triv + 3 * (size_t)(k - 1);
     if (tv[0] <= 0) continue;
@@ -772,6 +781,100 @@ __device__ int seed_srf(const unsigned long long *cell, int g, const Frame *fr, 
     if (bid != 0xFFFFFFFFu) return (int)bid;
   }
   return 0;
+}
+
+// ---------------------------------------------------------------- point map (USE_POINTMAP)
+//
+// With USE_POINTMAP Mmg records in MMG5_Point.src the old-mesh vertex a new
+// point descends from, and PMMG_locate_setStart (src/locate_pmmg.c:931-986)
+// turns it into a start element per point: the first tria (boundary points)
+// or tetra (the others) holding that vertex.  The start tables hold, per
+// background vertex, the lowest-index in-use tetra / boundary tria with the
+// vertex, 0 when there is none: the result of that function's ascending loops
+// with their `if (s) continue` guards (it visits every tetra; the packed tetv
+// marks unused ones with v[0] <= 0 and they are skipped here).  The tables are
+// built as unsigned minima of id - 1 over a table preset to 0xFFFFFFFF, then
+// shifted back by k_start_fin (0xFFFFFFFF + 1 = 0: none), so the result does
+// not depend on the order the blocks run in.  Blocks mostly run in ascending
+// order, so the plain load that finds a lower id already stored spares almost
+// every atomic (a stale value read there only costs an atomic more).
+__device__ __forceinline__ void start_min(unsigned *tab, int np, int v, unsigned key) {
+  const unsigned u = (unsigned)v - 1u;
+  if (u >= (unsigned)np) return; // (ids outside [1, np] index nothing)
+  if (tab[u] > key) atomicMin(&tab[u], key);
+}
+
+__global__ __launch_bounds__(kBlock) void k_start_tet(Bg bg, unsigned *tab) {
+  const long long nth = (long long)gridDim.x * blockDim.x;
+  for (long long k = 1 + blockIdx.x * (long long)blockDim.x + threadIdx.x; k <= bg.ne; k += nth) {
+    const int4 tv = tetv_row(bg, (int)k);
+    if (tv.x <= 0) continue; // unused tetra
+    const unsigned key = (unsigned)(k - 1);
+    start_min(tab, bg.np, tv.x, key);
+    start_min(tab, bg.np, tv.y, key);
+    start_min(tab, bg.np, tv.z, key);
+    start_min(tab, bg.np, tv.w, key);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_start_tri(Bg bg, unsigned *tab) {
+  const long long nth = (long long)gridDim.x * blockDim.x;
+  for (long long k = 1 + blockIdx.x * (long long)blockDim.x + threadIdx.x; k <= bg.nt; k += nth) {
+    const int *tv = bg.triv + 3 * (size_t)(k - 1);
+    const unsigned key = (unsigned)(k - 1);
+    for (int j = 0; j < 3; j++) start_min(tab, bg.np, tv[j], key);
+  }
+}
+
+// id - 1 minima -> 1-based ids, 0 = none (both tables: n = 2 * np)
+__global__ __launch_bounds__(kBlock) void k_start_fin(unsigned *tab, long long n) {
+  const long long nth = (long long)gridDim.x * blockDim.x;
+  for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < n; j += nth) tab[j] += 1u;
+}
+
+// The point map of one call: src[ip - 1] = 1-based background vertex of new
+// point ip (0 = unknown) and the background's start tables.
+struct MapArgs {
+  const int *src;
+  const int *start_tet, *start_tri;
+};
+
+// The start element the map gives point ip in a table over nel elements, 0
+// when it gives none.  Both range tests are unsigned compares made before the
+// value indexes anything: a source outside [1, np] counts as unknown, and so
+// does a table entry outside [1, nel].
+__device__ __forceinline__ int map_start(const int *src, const int *tab, int np, int nel, int ip, bool nt_load) {
+  const unsigned v = (unsigned)(nt_load ? __builtin_nontemporal_load(src + ip - 1) : src[ip - 1]) - 1u;
+  if (v >= (unsigned)np) return 0;
+  const unsigned k = (unsigned)tab[v] - 1u;
+  return k < (unsigned)nel ? (int)(k + 1u) : 0;
+}
+
+// need[0] / need[1] (zeroed before the launch): the volume / surface queries
+// the map gives no start, which take the seed grids; k_seed_vol / k_seed_srf
+// return at once when theirs is zero
+__global__ __launch_bounds__(kBlock) void k_map_count(const uint8_t *pclass, long long np_new, MapArgs ma, int np,
+                                                      int ne, int nt, int *need) {
+  __shared__ int cnt[2];
+  if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const long long nth = (long long)gridDim.x * blockDim.x;
+  int nv = 0, nb = 0;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < np_new; i += nth) {
+    const int cls = __builtin_nontemporal_load(pclass + i);
+    if (cls == PMMG_PT_VOL) nv += map_start(ma.src, ma.start_tet, np, ne, (int)i + 1, false) == 0;
+    else if (cls == PMMG_PT_BDY) nb += map_start(ma.src, ma.start_tri, np, nt, (int)i + 1, false) == 0;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    nv += __shfl_down(nv, o);
+    nb += __shfl_down(nb, o);
+  }
+  if (__lane_id() == 0) {
+    if (nv) atomicAdd(&cnt[0], nv);
+    if (nb) atomicAdd(&cnt[1], nb);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(&need[threadIdx.x], cnt[threadIdx.x]);
 }
 
 // ---------------------------------------------------------------- block scans

@@ -1013,13 +1013,18 @@ __device__ __forceinline__ void vol_interp_wave(const Slots &S, bool acc, VolLoc
 // PK: 0 = one array per solution, 1 / 2 = packed records in 1 / 2 passes.
 // lb.v non-null (split volume stage, r06; launched as the locate-only layout):
 // the located records go to lb and k_vol_interp interpolates them.
-template <int PK, int C0, int C1, int C2, int C3, int C4, int C5>
+// MAP = 1 (a call with a point map, pmmg_hip_set_point_map): a query whose
+// source vertex has a start tetra begins its filter walk there instead of at
+// the seed grid's tetra (PMMG_locate_setStart, the USE_POINTMAP branch of
+// src/interpmesh_pmmg.c:602-604).  A variant of its own, with ma the last
+// argument: the plain instantiations keep their code and register budget.
+template <int PK, int C0, int C1, int C2, int C3, int C4, int C5, int MAP = 0>
 __global__ __launch_bounds__(64) void k_vol(Bg bg, const Frame *fr, const unsigned long long *grid, int g,
                                             const double *qxyz, const uint8_t *pclass, const int *order,
                                             const double *qs, int np, ContEntry *cont, DevStats *st, Slots S,
                                             int *elem_out, int8_t *hit_out, int filter_steps,
                                             const int *order_flag, int xcd_run, int pad, int want, LocBuf lb,
-                                            int blk0, ContArgs ca) {
+                                            int blk0, ContArgs ca, MapArgs ma) {
   // want >= 0: the launch for one of the two orders (auto mode launches both, each after its own lists;
   // the other returns at once)
   if (want >= 0 && order_flag[0] != want) return;
@@ -1043,6 +1048,7 @@ __global__ __launch_bounds__(64) void k_vol(Bg bg, const Frame *fr, const unsign
   double x[3];
   int4 tv = make_int4(1, 1, 1, 1);
   bool noseed = false;
+  [[maybe_unused]] bool mapped = false; // (MAP: the walk began from the point map)
   // the queries' coordinates, streamed once (non-temporal).  In input order
   // (and in the binning's processing-order copy) the wave's 64 rows are one
   // contiguous 1.5 KiB block: two instructions of 16-byte pieces through LDS
@@ -1073,7 +1079,11 @@ __global__ __launch_bounds__(64) void k_vol(Bg bg, const Frame *fr, const unsign
     }
   }
   if (active) {
-    k = seed_vol(grid, g, fr, x, noseed);
+    if constexpr (MAP != 0) { // (input order: src is streamed once; Morton order gathers it)
+      k = map_start(ma.src, ma.start_tet, bg.np, bg.ne, ip, !sorted);
+      mapped = k != 0;
+    }
+    if (MAP == 0 || k == 0) k = seed_vol(grid, g, fr, x, noseed);
     if (k == 0) {
       status = 2;
     } else {
@@ -1166,6 +1176,7 @@ __global__ __launch_bounds__(64) void k_vol(Bg bg, const Frame *fr, const unsign
   wave_count(&sh.bs, kCntVolQueries, active);
   wave_count(&sh.bs, kCntExact, more);
   wave_count(&sh.bs, kCntNoSeed, active && noseed);
+  if constexpr (MAP != 0) wave_count(&sh.bs, kCntVolSrc, active && mapped);
   if (lb.v && (sorted ? i < st->nvol : i < np)) { // split stage: the located record of processing index i
     __builtin_nontemporal_store(acc ? nti4{loc.v.x, loc.v.y, loc.v.z, loc.v.w} : nti4{0, 0, 0, 0}, lb.v + i);
     if (acc) {

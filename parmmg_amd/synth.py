@@ -185,6 +185,43 @@ def cell_stats(m: Mesh) -> dict:
             "min_volume": float(vol.min())}
 
 
+def point_map(bg: Mesh, xyz_new: np.ndarray, elem: np.ndarray | None = None, pclass: np.ndarray | None = None,
+              stale: bool = False, seed: int = SEED, chunk: int = 2048) -> np.ndarray:
+    """A synthetic point map (Mmg's MMG5_Point.src under USE_POINTMAP): per new
+    point the 1-based background vertex it "descends from", int32.
+
+    elem None: the nearest background vertex, by brute force in chunks of
+    `chunk` points (test sizes: np_new x np distances).  elem given (the
+    located elements of a transfer, with pclass: a tetra for class 1, a
+    boundary tria for class 2; other points and elem 0 -> 0 = unknown): the
+    nearest of the element's vertices — or, stale=True, a random one of them
+    (a map that aged through a few more remeshing operations)."""
+    xyz_new = np.asarray(xyz_new, np.float64)
+    n = xyz_new.shape[0]
+    src = np.zeros(n, np.int32)
+    if elem is None:
+        for a in range(0, n, chunk):
+            d = xyz_new[a:a + chunk, None, :] - bg.xyz[None, :, :]
+            src[a:a + chunk] = np.argmin(np.einsum("ijk,ijk->ij", d, d), axis=1) + 1
+        return src
+    if pclass is None:
+        raise ValueError("point_map: located elements need the points' classes")
+    elem = np.asarray(elem, np.int64)
+    rng = np.random.default_rng(seed)
+    for cls, conn in ((1, bg.tetv), (2, bg.triv)):
+        idx = np.nonzero((np.asarray(pclass) == cls) & (elem >= 1) & (elem <= conn.shape[0]))[0]
+        for a in range(0, idx.size, 1 << 20):
+            ii = idx[a:a + (1 << 20)]
+            v = conn[elem[ii] - 1]  # (m, 4 | 3) vertex ids
+            if stale:
+                pick = rng.integers(0, v.shape[1], ii.size)
+            else:
+                d = bg.xyz[v - 1] - xyz_new[ii, None, :]
+                pick = np.argmin(np.einsum("ijk,ijk->ij", d, d), axis=1)
+            src[ii] = v[np.arange(ii.size), pick]
+    return src
+
+
 def mmg_like_perm(nq: int) -> np.ndarray:
     """A numbering of the new points like Mmg's output after an adaptation
     (src/libparmmg1.c:692-741: the group is renumbered, then Mmg keeps the

@@ -220,6 +220,28 @@ class TransferContext:
         self._ck(self.lib.pmmg_hip_set_solutions_packed(self.h, int(met_size), len(field_sizes), sizes, _p(rec),
                                                         where), "set_solutions_packed")
 
+    def set_point_map(self, src) -> None:
+        """pmmg_hip_set_point_map: arms the next locate_interp / locate_interp_rec
+        with Mmg's point map — src[i] = 1-based background vertex new point i+1
+        descends from (MMG5_Point.src under USE_POINTMAP), 0 = unknown.  A numpy
+        array is copied; a device array must stay valid until the call is done."""
+        if not _is_dev(src):
+            src = np.ascontiguousarray(src, np.int32)
+        elif np.dtype(src.dtype) != np.int32:
+            raise ValueError("a device point map must be int32")
+        self._map_keep = src
+        self._ck(self.lib.pmmg_hip_set_point_map(self.h, int(src.shape[0]), _p(src),
+                                                 DEVICE if _is_dev(src) else HOST), "set_point_map")
+
+    def start_elements(self):
+        """pmmg_hip_start_elements: (start_tet, start_tri) of the background as
+        set, per vertex the lowest-index in-use tetra / boundary tria holding
+        it (1-based, 0 = none): PMMG_locate_setStart's start elements."""
+        npt = self._keep[0].shape[0]
+        st, sr = np.zeros(npt, np.int32), np.zeros(npt, np.int32)
+        self._ck(self.lib.pmmg_hip_start_elements(self.h, _p(st), _p(sr), HOST), "start_elements")
+        return st, sr
+
     def locate_interp(self, xyz_new, pclass, met_out, fields_out, elem_out=None, hit_out=None,
                       sync: bool = True) -> HipStats | None:
         where = DEVICE if _is_dev(xyz_new) else HOST
@@ -439,7 +461,8 @@ class _Groups:
             self.keep += [fsz, fpt, gpt]
 
 
-def interp_metrics_and_fields(ctx: TransferContext, old_groups, new_groups, input_met: int = 1, carry=None):
+def interp_metrics_and_fields(ctx: TransferContext, old_groups, new_groups, input_met: int = 1, carry=None,
+                              src=None):
     """PMMG_interpMetricsAndFields over groups (src/interpmesh_pmmg.c:663-741)
     through the C host layer (pmmg_interp_metrics_and_fields).  The new
     groups' ``met`` / ``fields`` arrays are filled in place; per-group
@@ -448,9 +471,23 @@ def interp_metrics_and_fields(ctx: TransferContext, old_groups, new_groups, inpu
     pmmg_interp_metrics_and_fields_carry — the new groups stay on the device,
     and with carried the old groups are the previous call's new groups (src:
     None, or per group None / the 1-based map of its vertices onto them).
+    src: per group None / Mmg's point map of its new points (MMG5_Point.src,
+    1-based old-group vertex, 0 = unknown) for
+    pmmg_interp_metrics_and_fields_map; not together with carry.
     Returns (ier, stats)."""
     G = _Groups(old_groups, new_groups)
     st = HipStats()
+    if src is not None:
+        if carry is not None:
+            raise ValueError("interp_metrics_and_fields: src= and carry= are separate entry points")
+        arrs = [None if m is None else np.ascontiguousarray(m, np.int32) for m in src]
+        maps = (ctypes.c_void_p * max(1, len(arrs)))(*[None if a is None else _p(a).value for a in arrs])
+        G.keep.append(arrs)
+        ier = host_lib().pmmg_interp_metrics_and_fields_map(ctx.h, len(old_groups),
+                                                            ctypes.cast(G.olds, ctypes.c_void_p),
+                                                            ctypes.cast(G.news, ctypes.c_void_p), int(input_met),
+                                                            ctypes.cast(maps, ctypes.c_void_p), ctypes.byref(st))
+        return ier, st
     if carry is None:
         ier = host_lib().pmmg_interp_metrics_and_fields(ctx.h, len(old_groups), ctypes.cast(G.olds, ctypes.c_void_p),
                                                         ctypes.cast(G.news, ctypes.c_void_p), int(input_met),
