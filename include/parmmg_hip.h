@@ -268,7 +268,10 @@ int64_t pmmg_hip_bytes_up(pmmg_hip_ctx *ctx, int reset);
 /* Free the context's reusable scratch: the snapshot builders' buckets (12 B x
  * 4 x ne for the adjacency: ~4.8 GB at 101M tetra), the Morton binning's
  * second key / value arrays and digit tables, the point map's start tables
- * (pmmg_hip_start_elements), and the group lanes (contexts
+ * (pmmg_hip_start_elements), the scratch of pmmg_hip_qual_histo /
+ * pmmg_hip_edge_lengths (the edge table, 12 B x (12 np + 2 nskip) slots: ~2.9 GB
+ * at cfg4's adapted mesh of 20.35M points; one ownership byte per tetra; the
+ * per-block slabs, under 1 MB), and the group lanes (contexts
  * of their own, re-created by the next groups call).  The next call that
  * needs any of them allocates it again.  Waits for the context's work first.
  * The background, solutions, kept slots and seed grids stay.  Returns 1/0. */
@@ -370,6 +373,84 @@ int pmmg_hip_build_boundary(pmmg_hip_ctx *ctx, int np, int ne, const int *tet8,
 int pmmg_hip_tetra_qual(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne,
                         const int *tetv, int met_size, const double *met,
                         double *qual, double *minqual);
+
+/* ---- Reports on the adapted mesh in its interpolated metric -------------------
+ * The two reports ParMmg prints after an adaptation, reduced on the device
+ * from arrays that are already there (the metric where pmmg_hip_locate_interp
+ * wrote it, qual where pmmg_hip_tetra_qual wrote it).  Device pointers,
+ * 1-based vertex ids, synchronous, main stream only; return 1, or 0 with
+ * pmmg_hip_last_error.  Both structs end in a zeroed reserved[4]; a shim
+ * checks pmmg_hip_qual_histo_size() / pmmg_hip_len_histo_size() against its
+ * sizeof at load, as it checks pmmg_hip_stats_size(). */
+
+/* Quality histogram of one group: the per-group MMG3D_computeOutqua call of
+ * PMMG_qualhisto (src/quality_pmmg.c:156-345, called at src/libparmmg1.c:910);
+ * the MPI reductions of :275-304 stay on the host.  Restated from Mmg
+ * @889d408, which is not in the image: parity unpinned.  With
+ * rap = MMG3D_ALPHAD * qual[k] over the used tetra (tetv[4k] > 0): */
+typedef struct {
+  int64_t ne_used;     /* used tetra */
+  double max;          /* largest rap (start value 0) */
+  double min;          /* smallest rap (start value 2: none used, as pmmg_hip_tetra_qual) */
+  int64_t iel;         /* 1-based row of the lowest-index used tetra attaining min, 0 when none; Mmg's
+                          ordinal for a packed mesh (MMG5_paktet, src/libparmmg1.c:769) */
+  double avg_sum;      /* sum of rap: the caller divides (src/quality_pmmg.c:322, after its MPI_Reduce) */
+  int64_t good;        /* rap > 0.12 */
+  int64_t med;         /* rap > 0.5 */
+  int64_t his[5];      /* bin min(4, (int)(5 rap)) */
+  int64_t reserved[4]; /* zero.  Mmg's ridge-point count nrid needs its point tags: not modelled */
+} pmmg_hip_qual_histo_t;
+int64_t pmmg_hip_qual_histo_size(void);
+
+/* qual[ne] as pmmg_hip_tetra_qual wrote it, tetv[4*ne] 16-byte aligned.
+ * Two calls on the same inputs fill byte-identical structs (avg_sum is summed
+ * in a fixed order). */
+int pmmg_hip_qual_histo(pmmg_hip_ctx *ctx, int ne, const int *tetv, const double *qual,
+                        pmmg_hip_qual_histo_t *out);
+
+/* Edge lengths in the metric: the body of PMMG_computePrilen
+ * (src/quality_pmmg.c:370-574; PMMG_prilen :591-715 prints it), over every
+ * unique edge {a, b} of the used tetra.  The owner of an edge is the
+ * lowest-index used tetra holding it and, in that tetra, its lowest local
+ * edge ia in MMG5_iare order: what MMG5_hashPop leaves in the ascending loop
+ * of :506-564.  Its length is taken there, from (np, nq) = (v[iare[ia][0]],
+ * v[iare[ia][1]]), with MMG5_lenedg (met_size 1: MMG5_lenedgCoor_iso, 6:
+ * MMG5_lenedgCoor_ani, restated from Mmg @889d408: parity unpinned; any other
+ * met_size returns 0).  Not modelled, as in pmmg_hip_compute_wgt_*: Mmg's
+ * metric storage at ridge points and the MG_GEO point filter of :510-517. */
+typedef struct {
+  int64_t nedge;       /* unique edges, skipped ones included */
+  int64_t nskipped;    /* mesh edges found in the skip list: counted here and nowhere else */
+  int64_t ned;         /* analysed edges with len != 0 */
+  int64_t nnull;       /* analysed edges with len == 0 */
+  double avlen_sum;    /* sum of len over the ned edges, in a fixed order (the caller divides) */
+  double lmin;         /* shortest of them (start value 1e30), strict <: ties go to the earlier (owner, ia) */
+  double lmax;         /* longest (start value 0), strict > */
+  int32_t amin, bmin;  /* (np, nq) of the shortest edge at its owner, 0 when there is none */
+  int32_t amax, bmax;  /* of the longest */
+  int64_t hl[9];       /* hl[i] for the first i < 8 with bd[i] <= len && len < bd[i+1], else hl[8], bd = 0,
+                          0.3, 0.6, 0.7071, 0.9, 1.3, 1.4142, 2, 5 (:489-495: a NaN length lands in
+                          hl[8] and moves neither extreme) */
+  int64_t reserved[4]; /* zero */
+} pmmg_hip_len_histo_t;
+int64_t pmmg_hip_len_histo_size(void);
+
+/*   skip[2*nskip]     (NULL with nskip 0) vertex-id pairs, any orientation, repeats allowed: the parallel
+ *                     edges a lower rank owns (:412-452).  A pair that is no mesh edge is ignored.
+ *   edge_out[2*cap], len_out[cap]   (either may be NULL) the analysed edges (skipped ones left out, null
+ *                     ones included) as (np, nq) and their lengths, in ascending (owner tetra, ia)
+ *                     order.  When cap < nedge - nskipped nothing is written to them, *out is still
+ *                     filled and 0 is returned (pmmg_hip_build_boundary's convention).
+ * A vertex id of a used tetra outside [1, np] returns 0.  tetv 16-byte, skip / edge_out / len_out 8-byte
+ * aligned; needs 6 ne < 2^32.  The edge table lives in the context (pmmg_hip_release_scratch).
+ * Two calls on the same inputs give byte-identical out, edge_out and len_out. */
+int pmmg_hip_edge_lengths(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne, const int *tetv,
+                          int met_size, const double *met, int nskip, const int *skip,
+                          pmmg_hip_len_histo_t *out, int cap, int *edge_out, double *len_out);
+
+/* Device bytes of the two reports' scratch held by the context (edge table, slabs; 0 after
+ * pmmg_hip_release_scratch). */
+int64_t pmmg_hip_mesh_stats_bytes(pmmg_hip_ctx *ctx);
 
 /* Solutions as packed per-vertex records: rec[RS*np], vertex v's record at
  * rec + RS*(v-1) = [metric (met_size) | field 0 | field 1 | ...] with

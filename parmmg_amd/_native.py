@@ -38,6 +38,35 @@ class HipStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class HipQualHisto(ctypes.Structure):
+    """``pmmg_hip_qual_histo_t`` of include/parmmg_hip.h."""
+
+    _fields_ = [
+        ("ne_used", c_int64), ("max", c_double), ("min", c_double), ("iel", c_int64), ("avg_sum", c_double),
+        ("good", c_int64), ("med", c_int64), ("his", c_int64 * 5), ("reserved", c_int64 * 4),
+    ]
+
+    def as_dict(self) -> dict:
+        d = {name: getattr(self, name) for name, _ in self._fields_ if name not in ("his", "reserved")}
+        d["his"] = list(self.his)
+        return d
+
+
+class HipLenHisto(ctypes.Structure):
+    """``pmmg_hip_len_histo_t`` of include/parmmg_hip.h."""
+
+    _fields_ = [
+        ("nedge", c_int64), ("nskipped", c_int64), ("ned", c_int64), ("nnull", c_int64), ("avlen_sum", c_double),
+        ("lmin", c_double), ("lmax", c_double), ("amin", ctypes.c_int32), ("bmin", ctypes.c_int32),
+        ("amax", ctypes.c_int32), ("bmax", ctypes.c_int32), ("hl", c_int64 * 9), ("reserved", c_int64 * 4),
+    ]
+
+    def as_dict(self) -> dict:
+        d = {name: getattr(self, name) for name, _ in self._fields_ if name not in ("hl", "reserved")}
+        d["hl"] = list(self.hl)
+        return d
+
+
 class HipGroup(ctypes.Structure):
     """``pmmg_hip_group`` of include/parmmg_hip.h (device pointers)."""
 
@@ -83,6 +112,12 @@ HIP_API = {
                                            c_void_p]),
     "pmmg_hip_tetra_qual": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                     P(c_double)]),
+    "pmmg_hip_qual_histo_size": (c_int64, []),
+    "pmmg_hip_len_histo_size": (c_int64, []),
+    "pmmg_hip_qual_histo": (c_int, [c_void_p, c_int, c_void_p, c_void_p, P(HipQualHisto)]),
+    "pmmg_hip_edge_lengths": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                      P(HipLenHisto), c_int, c_void_p, c_void_p]),
+    "pmmg_hip_mesh_stats_bytes": (c_int64, [c_void_p]),
     "pmmg_hip_memcpy_h2d": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "pmmg_hip_memcpy_d2h": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "pmmg_hip_locate_interp_rec": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -131,6 +166,11 @@ def hip_lib() -> ctypes.CDLL:
     # PMMG_HIP_SO: an alternative build of the same module (A/B measurements)
     lib = _load(os.environ.get("PMMG_HIP_SO", _build.HIP_SO), HIP_API, "libpmmg_hip.so")
     # the load-time ABI check a shim makes (include/parmmg_hip.h, PMMG_HIP_ABI_VERSION)
+    if (lib.pmmg_hip_qual_histo_size() != ctypes.sizeof(HipQualHisto)
+            or lib.pmmg_hip_len_histo_size() != ctypes.sizeof(HipLenHisto)):
+        raise RuntimeError(f"libpmmg_hip.so report structs {lib.pmmg_hip_qual_histo_size()} / "
+                           f"{lib.pmmg_hip_len_histo_size()} B, expected {ctypes.sizeof(HipQualHisto)} / "
+                           f"{ctypes.sizeof(HipLenHisto)} B: rebuild (python -m parmmg_amd.build)")
     if lib.pmmg_hip_abi_version() != ABI_VERSION or lib.pmmg_hip_stats_size() != ctypes.sizeof(HipStats):
         raise RuntimeError(f"libpmmg_hip.so ABI {lib.pmmg_hip_abi_version()} / stats {lib.pmmg_hip_stats_size()} B, "
                            f"expected {ABI_VERSION} / {ctypes.sizeof(HipStats)} B: rebuild (python -m parmmg_amd.build)")

@@ -62,9 +62,11 @@ def build_hip(force: bool = False, measure: bool = False) -> str:
     src = os.path.join(CSRC, "pmmg_hip.hip")
     snap = os.path.join(CSRC, "pmmg_snapshot.hip")
     qual = os.path.join(CSRC, "pmmg_quality.hip")
-    deps = [src, snap, qual, os.path.join(INC, "parmmg_hip.h"), __file__] + [
+    mstats = os.path.join(CSRC, "pmmg_meshstats.hip")
+    deps = [src, snap, qual, mstats, os.path.join(INC, "parmmg_hip.h"), __file__] + [
         os.path.join(CSRC, h) for h in ("pmmg_device.hpp", "pmmg_prep.hpp", "pmmg_vol.hpp", "pmmg_bdy.hpp",
                                         "pmmg_fallback.hpp", "pmmg_snapshot.hpp", "pmmg_quality.hpp",
+                                        "pmmg_meshstats.hpp",
                                         "pmmg_brick.hpp", "pmmg_sort.hpp")]
     if force or _stale(out, deps):
         # max-memory-clause scheduling: the gathers of a step issued as clauses
@@ -73,7 +75,7 @@ def build_hip(force: bool = False, measure: bool = False) -> str:
               "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
               # (r05: flowing off a lambda that a `return 0` made non-void is undefined: a host segfault)
               "-Werror=return-type"] + (["-DPMMG_HIP_MEASURE"] if measure else []) +
-             [f"-I{INC}", "-o", out, src, snap, qual])
+             [f"-I{INC}", "-o", out, src, snap, qual, mstats])
     return out
 
 

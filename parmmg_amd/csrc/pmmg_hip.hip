@@ -54,6 +54,7 @@
 #include "pmmg_fallback.hpp"
 #include "pmmg_snapshot.hpp"
 #include "pmmg_quality.hpp"
+#include "pmmg_meshstats.hpp"
 #include "pmmg_comm.hpp"
 
 using namespace pmmg;
@@ -239,6 +240,9 @@ struct pmmg_hip_ctx {
   struct Pool *pool = nullptr;
   DevBuf o_tet4; // device copy of a host tetv (input of the device adjacency)
   SnapCache snap_cache; // the snapshot kernels' scratch (pmmg_snapshot.hip)
+  StatsCache stats_cache; // pmmg_hip_qual_histo / pmmg_hip_edge_lengths: edge table, slabs (pmmg_meshstats.hip)
+  int edge_hash = 1;      // the edge table's slot: 1 a run of slots per low vertex first, 0 a mix of the whole
+                          // key (PMMG_HIP_EDGEHASH=0; cfg4: 31.0 against 56.0 ms)
   // host mode: the device-built background (adjacency, boundary trias) runs
   // on `stream` in a host thread while set_solutions' uploads go through
   // `cstream` (the DMA engine works beside the snapshot kernels); every other
@@ -700,6 +704,8 @@ extern "C" {
 
 int pmmg_hip_abi_version(void) { return PMMG_HIP_ABI_VERSION; }
 int64_t pmmg_hip_stats_size(void) { return (int64_t)sizeof(pmmg_hip_stats); }
+int64_t pmmg_hip_qual_histo_size(void) { return (int64_t)sizeof(pmmg_hip_qual_histo_t); }
+int64_t pmmg_hip_len_histo_size(void) { return (int64_t)sizeof(pmmg_hip_len_histo_t); }
 
 int pmmg_hip_device_count(void) {
   int n = 0;
@@ -752,6 +758,7 @@ static pmmg_hip_ctx *create_ctx(int device, int options, bool srf_prio, pmmg_hip
   c->srf_mult = std::min(4096, env_int("PMMG_HIP_SRFMULT", c->srf_mult));
   c->bin_bits = std::min(7, env_int("PMMG_HIP_BINBITS", c->bin_bits));
   c->verbose = env_int("PMMG_HIP_VERBOSE", 0);
+  c->edge_hash = env_int_any("PMMG_HIP_EDGEHASH", 1) == 0 ? 0 : 1;
   c->maxstep = env_int("PMMG_HIP_MAXSTEP", c->maxstep);
   c->group_lanes = std::min(16, env_int("PMMG_HIP_GROUP_LANES", c->group_lanes));
   // test-only path selection (tests/test_gpu_hits.py, tests/test_gpu_parity.py)
@@ -851,6 +858,7 @@ void pmmg_hip_destroy(pmmg_hip_ctx *c) {
   delete c->pool;
   release(c->o_tet4);
   pmmg_snap_cache_free(&c->snap_cache);
+  pmmg_stats_cache_free(&c->stats_cache);
   for (auto &k : c->kept) {
     release(k.xyz);
     release(k.met);
@@ -2334,6 +2342,7 @@ int pmmg_hip_release_scratch(pmmg_hip_ctx *c) {
   HIPCK(c, hipStreamSynchronize(c->stream2));
   if (c->stream3) HIPCK(c, hipStreamSynchronize(c->stream3));
   pmmg_snap_cache_free(&c->snap_cache);
+  pmmg_stats_cache_free(&c->stats_cache);
   for (DevBuf *b : {&c->bvals2, &c->rs_hist, &c->rs_csum, &c->start_tab}) release(*b);
   c->start_valid = false; // (the next call with a point map builds the start tables again)
   for (pmmg_hip_ctx *l : c->lanes) pmmg_hip_destroy(l);
@@ -2537,6 +2546,46 @@ int pmmg_hip_tetra_qual(pmmg_hip_ctx *c, int np, const double *xyz, int ne, cons
   *minqual = alphad * mn;
   return 1;
 }
+
+int pmmg_hip_qual_histo(pmmg_hip_ctx *c, int ne, const int *tetv, const double *qual, pmmg_hip_qual_histo_t *out) {
+  if (!c) return 0;
+  HIPCK(c, hipSetDevice(c->device));
+  if (!snap_join(c)) return 0;
+  if (ne < 0 || (ne > 0 && (!tetv || !qual)) || !out) {
+    set_err(c, "qual_histo: invalid arguments (ne=%d)", ne);
+    return 0;
+  }
+  if (ne > 0 && !aligned16(tetv)) {
+    set_err(c, "qual_histo: tetv must be 16-byte aligned");
+    return 0;
+  }
+  return pmmg_stats_qual_histo(c->stream, ne, tetv, qual, out, &c->stats_cache, c->err, sizeof(c->err));
+}
+
+int pmmg_hip_edge_lengths(pmmg_hip_ctx *c, int np, const double *xyz, int ne, const int *tetv, int met_size,
+                          const double *met, int nskip, const int *skip, pmmg_hip_len_histo_t *out, int cap,
+                          int *edge_out, double *len_out) {
+  if (!c) return 0;
+  HIPCK(c, hipSetDevice(c->device));
+  if (!snap_join(c)) return 0;
+  if (met_size != 1 && met_size != 6) {
+    set_err(c, "edge_lengths: met_size %d (an edge length needs an iso (1) or aniso (6) metric)", met_size);
+    return 0;
+  }
+  if (np < 0 || ne < 0 || (ne > 0 && (np < 1 || !xyz || !tetv || !met)) || nskip < 0 || (nskip > 0 && !skip) || !out ||
+      cap < 0) {
+    set_err(c, "edge_lengths: invalid arguments (np=%d ne=%d nskip=%d cap=%d)", np, ne, nskip, cap);
+    return 0;
+  }
+  if ((ne > 0 && !aligned16(tetv)) || ((uintptr_t)skip & 7) || ((uintptr_t)edge_out & 7) || ((uintptr_t)len_out & 7)) {
+    set_err(c, "edge_lengths: tetv must be 16-byte, skip / edge_out / len_out 8-byte aligned");
+    return 0;
+  }
+  return pmmg_stats_edge_lengths(c->stream, np, xyz, ne, tetv, met_size, met, nskip, skip, out, cap, edge_out, len_out,
+                                 c->edge_hash, &c->stats_cache, c->err, sizeof(c->err));
+}
+
+int64_t pmmg_hip_mesh_stats_bytes(pmmg_hip_ctx *c) { return c ? pmmg_stats_cache_bytes(&c->stats_cache) : -1; }
 
 int pmmg_hip_compute_wgt_mesh(pmmg_hip_ctx *c, int np, const double *xyz, int ne, const int *tetv, const int *xt,
                               const uint16_t *ftag, int met_size, const double *met, int tag, double *qual) {

@@ -137,26 +137,9 @@ __global__ __launch_bounds__(kQBlock) void k_tetra_qual(const double *xyz, int n
 // interfaces.  Same operation order as oracle/pmmg_oracle.c orc_face_wgt;
 // exp / log1p are the device library's (within an ulp of the host's).
 constexpr double kHugeWgt = 1000000.0; // PMMG_WGTVAL_HUGEINT
-constexpr double kMmgEps = 1.0e-06;    // MMG5_EPS
+// (lenedg_iso / lenedg_ani and MMG5_EPS: pmmg_quality.hpp, shared with pmmg_meshstats.hip)
 __constant__ int kIare[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}}; // MMG5_iare
 __constant__ int kIarf[4][3] = {{5, 4, 3}, {5, 1, 2}, {4, 2, 0}, {3, 0, 1}};     // MMG5_iarf
-
-__device__ __forceinline__ double lenedg_iso(const double *ca, const double *cb, double h1, double h2) {
-  double l = (cb[0] - ca[0]) * (cb[0] - ca[0]) + (cb[1] - ca[1]) * (cb[1] - ca[1]) + (cb[2] - ca[2]) * (cb[2] - ca[2]);
-  l = sqrt(l);
-  const double r = h2 / h1 - 1.0;
-  return (fabs(r) < kMmgEps) ? (l / h1) : (l / (h2 - h1) * log1p(r));
-}
-
-__device__ __forceinline__ double lenedg_ani(const double *ca, const double *cb, const double *sa, const double *sb) {
-  const double ux = cb[0] - ca[0], uy = cb[1] - ca[1], uz = cb[2] - ca[2];
-  double dd1 = sa[0] * ux * ux + sa[3] * uy * uy + sa[5] * uz * uz + 2.0 * (sa[1] * ux * uy + sa[2] * ux * uz + sa[4] * uy * uz);
-  if (dd1 <= 0.0) dd1 = 0.0;
-  double dd2 = sb[0] * ux * ux + sb[3] * uy * uy + sb[5] * uz * uz + 2.0 * (sb[1] * ux * uy + sb[2] * ux * uz + sb[4] * uy * uz);
-  if (dd2 <= 0.0) dd2 = 0.0;
-  if (fabs(dd1 - dd2) < 0.05) return sqrt(0.5 * (dd1 + dd2));
-  return (sqrt(dd1) + sqrt(dd2) + 4.0 * sqrt(0.5 * (dd1 + dd2))) / 6.0;
-}
 
 __device__ double face_wgt(const double *xyz, const int *v, int ifac, int met_size, const double *met) {
   if (met_size != 1 && met_size != 6) return kHugeWgt;

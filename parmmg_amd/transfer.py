@@ -17,7 +17,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._native import HipGroup, HipStats, hip_lib, host_lib
+from ._native import HipGroup, HipLenHisto, HipQualHisto, HipStats, hip_lib, host_lib
 
 HOST, DEVICE = 0, 1
 PT_SKIP, PT_VOL, PT_BDY = 0, 1, 2
@@ -313,7 +313,8 @@ class TransferContext:
 
     def release_scratch(self) -> None:
         """pmmg_hip_release_scratch: free the snapshot buckets, the binning's
-        scratch and the group lanes (re-allocated on demand)."""
+        scratch, the reports' edge table and the group lanes (re-allocated on
+        demand)."""
         self._ck(self.lib.pmmg_hip_release_scratch(self.h), "release_scratch")
 
     def bytes_up(self, reset: bool = False) -> int:
@@ -333,6 +334,53 @@ class TransferContext:
                                               0 if met is None else int(met.shape[1]), _p(met), _p(qual),
                                               ctypes.byref(mn)), "tetra_qual")
         return qual, mn.value
+
+    def qual_histo(self, tetv, qual) -> dict:
+        """PMMG_qualhisto's per-group MMG3D_computeOutqua on the device
+        (pmmg_hip_qual_histo): device arrays, qual as tetra_qual wrote it.
+        Returns the struct as a dict (avg_sum is a sum: divide by ne_used)."""
+        if not (_is_dev(tetv) and _is_dev(qual)):
+            raise ValueError("qual_histo takes device arrays")
+        out = HipQualHisto()
+        self._ck(self.lib.pmmg_hip_qual_histo(self.h, tetv.shape[0], _p(tetv), _p(qual), ctypes.byref(out)),
+                 "qual_histo")
+        return out.as_dict()
+
+    def edge_lengths(self, xyz, tetv, met, skip=None, want_edges=False, cap=None):
+        """PMMG_computePrilen on the device (pmmg_hip_edge_lengths): device
+        arrays (the metric where locate_interp wrote it, [np, 1] or [np, 6]);
+        skip: device array [nskip, 2] of vertex-id pairs this rank must not
+        analyse, or None.  Returns the struct as a dict, or with want_edges
+        (dict, edges DeviceArray [n, 2], lengths DeviceArray [n]) in ascending
+        (owner tetra, local edge) order, n = nedge - nskipped; cap: rows to
+        allocate for the lists (None: one call without lists counts first)."""
+        if not (_is_dev(xyz) and _is_dev(tetv) and _is_dev(met)) or (skip is not None and not _is_dev(skip)):
+            raise ValueError("edge_lengths takes device arrays")
+        nskip = 0 if skip is None else int(skip.shape[0])
+
+        def call(cap_, edges, lens):
+            out = HipLenHisto()
+            ok = self.lib.pmmg_hip_edge_lengths(self.h, xyz.shape[0], _p(xyz), tetv.shape[0], _p(tetv),
+                                                int(met.shape[1]), _p(met), nskip, _p(skip), ctypes.byref(out),
+                                                int(cap_), _p(edges), _p(lens))
+            self._ck(ok, "edge_lengths")
+            return out
+
+        if not want_edges:
+            return call(0, None, None).as_dict()
+        if cap is None:
+            first = call(0, None, None)
+            cap = first.nedge - first.nskipped
+        edges, lens = self.empty((int(cap), 2), np.int32), self.empty((int(cap),), np.float64)
+        out = call(cap, edges, lens)
+        n = int(out.nedge - out.nskipped)
+        edges.shape, edges.nbytes = (n, 2), n * 8
+        lens.shape, lens.nbytes = (n,), n * 8
+        return out.as_dict(), edges, lens
+
+    def mesh_stats_bytes(self) -> int:
+        """device bytes of the two reports' scratch (pmmg_hip_mesh_stats_bytes)"""
+        return int(self.lib.pmmg_hip_mesh_stats_bytes(self.h))
 
     def compute_wgt_mesh(self, xyz, tetv, xt, ftag, met, tag, qual):
         """PMMG_computeWgt_mesh on the device (pmmg_hip_compute_wgt_mesh):
