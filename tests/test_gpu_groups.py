@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from parity import check, make_case, run_gpu
+from parity import assert_stats_match, check, make_case, run_gpu
 from parmmg_amd import synth
 from parmmg_amd.transfer import TransferContext, pack_tet8
 
@@ -80,6 +80,8 @@ def test_groups_match_single_calls(cases, singles, lanes, sync, monkeypatch):
             assert st.nbdy == sum(s["stats"]["nbdy"] for s in singles)
             assert st.steps_total == sum(s["stats"]["steps_total"] for s in singles)
             assert st.stepmax == max(s["stats"]["stepmax"] for s in singles)
+            # the summed counters against the groups' hit arrays
+            assert_stats_match(st, [c["pclass"] for c in cases], [g["hit_out"].download() for g in gs])
 
 
 @pytest.mark.gpu

@@ -25,7 +25,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from parity import check, make_case, run_gpu
+from parity import assert_stats_match, check, make_case, run_gpu
 from parmmg_amd import synth
 
 
@@ -55,6 +55,7 @@ def test_forced_exhaustive_hits(monkeypatch):
     print(rep, c)
     assert c[2] > 0 and c[9] > 0
     assert rep["class_i"] == rep["class_i_same"]
+    assert_stats_match(gpu["stats"], case["pclass"], gpu["hit"], maxstep=1)
 
 
 @pytest.mark.gpu

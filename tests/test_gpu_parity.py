@@ -5,7 +5,7 @@ contract is documented in tests/parity.py."""
 import numpy as np
 import pytest
 
-from parity import check, invmat_failure_case, make_case, run_gpu
+from parity import assert_stats_match, check, invmat_failure_case, make_case, run_gpu
 from parmmg_amd import synth
 
 C, S = synth.CUBE, synth.SHELL
@@ -72,6 +72,7 @@ def test_parity_small(name, mode):
     print(name, mode, rep, gpu["stats"])
     assert rep["n"] == int((case["pclass"] != 0).sum())
     assert rep["class_i"] == rep["class_i_same"]
+    assert_stats_match(gpu["stats"], case["pclass"], gpu["hit"], sort=MODES[mode].get("sort"))
 
 
 @pytest.mark.gpu
@@ -95,6 +96,7 @@ def test_fallback_paths_outside_domain(mode):
     rep = check(case, gpu)
     print(rep, gpu["stats"])
     assert gpu["stats"]["nvol_closest"] + gpu["stats"]["nvol_exhaust"] >= 1
+    assert_stats_match(gpu["stats"], case["pclass"], gpu["hit"], sort=MODES[mode].get("sort"))
 
 
 @pytest.mark.gpu
