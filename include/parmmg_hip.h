@@ -509,6 +509,53 @@ int pmmg_hip_compute_wgt_faces(pmmg_hip_ctx *ctx, int np, const double *xyz,
                                const int *tetv, int nface, const int *face,
                                int met_size, const double *met, double *wgt);
 
+/* ---- The METIS element graph of a group (src/metis_pmmg.c:746-823) ----------
+ * PMMG_graph_meshElts2metis on the device: the CSR dual graph of a group's
+ * tetra that PMMG_part_meshElts2metis (:1293) hands to METIS at the group
+ * split (src/grpsplit_pmmg.c:1698) and the distribution
+ * (src/distributemesh_pmmg.c:1026, :1139), from the adapted mesh and the
+ * metric where pmmg_hip_locate_interp wrote it.  Device pointers, 1-based
+ * vertex ids, synchronous, main stream only.
+ *   tetra   from tet8 (packed {v[4], adja[4]} records) when non-NULL, else
+ *           from tetv + adja; with tet8 == NULL && adja == NULL the adjacency
+ *           is built first (pmmg_hip_build_adjacency's kernels, into context
+ *           scratch): MMG3D_hashTetra's branch of :756, with that function's
+ *           failures and messages.  tetv may be NULL when adja is given and
+ *           adjwgt is NULL (every row then counts as used).
+ *   xadj[ne+1]      xadj[0] = 0, xadj[k] = non-zero adja entries of rows 0..k-1
+ *   adjncy[cap]     adja / 4 - 1 of every non-zero entry in ascending
+ *                   (tetra, face) order: the loop of :801-818
+ *   *nadjncy        (host) the entry count xadj[ne].  The reference's
+ *                   ++(*nadjncy) of :783 is slack for its allocation and is
+ *                   not reproduced.
+ *   adjwgt[cap]     (may be NULL: the unweighted graph of the distribution and
+ *                   of the last iteration, :790; xyz and met are then not
+ *                   touched and may be NULL)  max((int)w, 1) with w =
+ *                   PMMG_computeWgt of the face: for met_size 1 / 6 the bits
+ *                   pmmg_hip_compute_wgt_faces gives for that (tetra, face);
+ *                   met_size 0 (no metric): PMMG_WGTVAL_HUGEINT; a w that is
+ *                   not finite gives 1.  Mmg's metric storage at ridge points
+ *                   is not modelled (as in pmmg_hip_compute_wgt_*).
+ * An unused tetra (tetv row with v[0] <= 0) gets an empty row whatever its
+ * adja row holds.  Returns 0 (message in pmmg_hip_last_error), with nothing
+ * written to adjncy / adjwgt, when
+ *   - cap < *nadjncy: xadj and *nadjncy are still filled
+ *     (pmmg_hip_build_boundary's convention: call with cap 0 to size);
+ *   - an adja entry lies outside [4, 4*ne+3], or points to an unused tetra
+ *     (the reference requires a packed mesh);
+ *   - weights are asked and a used tetra has a vertex id outside [1, np];
+ *   - ne >= 2^29 (the 4*k+i encoding, as pmmg_hip_set_background).
+ * tet8 / tetv / adja / xyz / met 16-byte, xadj / adjncy / adjwgt 4-byte
+ * aligned.  idx_t is 32 bits (METIS 5.1.0's default IDXTYPEWIDTH); there is no
+ * 64-bit variant.  Per-block counts and a built adjacency live in the context
+ * (pmmg_hip_release_scratch).  Two calls on the same inputs give
+ * byte-identical outputs. */
+int pmmg_hip_metis_graph(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne,
+                         const int *tetv, const int *adja, const int *tet8,
+                         int met_size, const double *met,
+                         int cap, int64_t *nadjncy,
+                         int *xadj, int *adjncy, int *adjwgt);
+
 /* ---- One group split over the GPUs of a node -------------
  * One process per GPU (ParMmg's MPI ranks; GPU = node-local rank,
  * src/parmmg.c:121).  Each rank transfers its part of the group's new points

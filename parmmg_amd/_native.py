@@ -118,6 +118,8 @@ HIP_API = {
     "pmmg_hip_edge_lengths": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                       P(HipLenHisto), c_int, c_void_p, c_void_p]),
     "pmmg_hip_mesh_stats_bytes": (c_int64, [c_void_p]),
+    "pmmg_hip_metis_graph": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                     c_int, P(c_int64), c_void_p, c_void_p, c_void_p]),
     "pmmg_hip_memcpy_h2d": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "pmmg_hip_memcpy_d2h": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "pmmg_hip_locate_interp_rec": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -189,6 +191,9 @@ HOST_API = {
     "pmmg_interp_metrics_and_fields_map": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, P(HipStats)]),
     "pmmg_interp_metrics_and_fields_carry": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                                      P(HipStats)]),
+    "pmmg_graph_mesh_elts2metis": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                           P(P(c_int)), P(P(c_int)), P(P(c_int)), P(c_int64)]),
+    "pmmg_host_free": (None, [c_void_p]),
     "pmmg_max_tet_extent": (c_double, [c_int, c_void_p, c_int, c_void_p]),
     "pmmg_shard_mark": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                                 c_void_p, P(c_int64)]),

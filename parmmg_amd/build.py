@@ -63,10 +63,11 @@ def build_hip(force: bool = False, measure: bool = False) -> str:
     snap = os.path.join(CSRC, "pmmg_snapshot.hip")
     qual = os.path.join(CSRC, "pmmg_quality.hip")
     mstats = os.path.join(CSRC, "pmmg_meshstats.hip")
-    deps = [src, snap, qual, mstats, os.path.join(INC, "parmmg_hip.h"), __file__] + [
+    graph = os.path.join(CSRC, "pmmg_graph.hip")
+    deps = [src, snap, qual, mstats, graph, os.path.join(INC, "parmmg_hip.h"), __file__] + [
         os.path.join(CSRC, h) for h in ("pmmg_device.hpp", "pmmg_prep.hpp", "pmmg_vol.hpp", "pmmg_bdy.hpp",
                                         "pmmg_fallback.hpp", "pmmg_snapshot.hpp", "pmmg_quality.hpp",
-                                        "pmmg_meshstats.hpp",
+                                        "pmmg_meshstats.hpp", "pmmg_graph.hpp",
                                         "pmmg_brick.hpp", "pmmg_sort.hpp")]
     if force or _stale(out, deps):
         # max-memory-clause scheduling: the gathers of a step issued as clauses
@@ -75,7 +76,7 @@ def build_hip(force: bool = False, measure: bool = False) -> str:
               "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
               # (r05: flowing off a lambda that a `return 0` made non-void is undefined: a host segfault)
               "-Werror=return-type"] + (["-DPMMG_HIP_MEASURE"] if measure else []) +
-             [f"-I{INC}", "-o", out, src, snap, qual, mstats])
+             [f"-I{INC}", "-o", out, src, snap, qual, mstats, graph])
     return out
 
 

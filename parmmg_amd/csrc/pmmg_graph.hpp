@@ -1,0 +1,30 @@
+// pmmg_graph.hpp — internal interface of pmmg_graph.hip (the METIS element
+// graph of a group and its metric weights); the C-ABI wrapper lives in
+// pmmg_hip.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "pmmg_snapshot.hpp"
+
+// Device scratch of the graph passes, owned by a context and kept between
+// calls (grown, never shrunk): per-block counts and offsets, the scan's
+// temporary, the flags, and the adjacency of a call that came without one.
+// Freed by pmmg_graph_cache_free (pmmg_hip_release_scratch).
+struct GraphCache {
+  static constexpr int kSlots = 5;
+  void *p[kSlots] = {};
+  size_t cap[kSlots] = {};
+};
+void pmmg_graph_cache_free(GraphCache *c);
+
+// pmmg_hip_metis_graph on checked arguments.  Tetra rows are int4 rows
+// `tstride` / `astride` int4s apart (1: separate arrays, 2: tet8); tetv may be
+// NULL without weights (every row counts as used); adja NULL: built from tetv
+// into the cache (pmmg_snap_adjacency, which sets msg when it fails).
+// want_wgt 0: adjwgt, xyz and met are not touched.  *nadjncy on the host.
+// Synchronous.  Returns 1, or 0 with msg set.
+int pmmg_graph_metis(hipStream_t s, int np, const double *xyz, int ne, const int *tetv, int tstride, const int *adja,
+                     int astride, int want_wgt, int met_size, const double *met, int cap, int64_t *nadjncy, int *xadj,
+                     int *adjncy, int *adjwgt, GraphCache *cache, SnapCache *snap, char *msg, size_t msglen);

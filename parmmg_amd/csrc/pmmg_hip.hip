@@ -55,6 +55,7 @@
 #include "pmmg_snapshot.hpp"
 #include "pmmg_quality.hpp"
 #include "pmmg_meshstats.hpp"
+#include "pmmg_graph.hpp"
 #include "pmmg_comm.hpp"
 
 using namespace pmmg;
@@ -241,6 +242,7 @@ struct pmmg_hip_ctx {
   DevBuf o_tet4; // device copy of a host tetv (input of the device adjacency)
   SnapCache snap_cache; // the snapshot kernels' scratch (pmmg_snapshot.hip)
   StatsCache stats_cache; // pmmg_hip_qual_histo / pmmg_hip_edge_lengths: edge table, slabs (pmmg_meshstats.hip)
+  GraphCache graph_cache; // pmmg_hip_metis_graph: block counts, scan scratch, a built adjacency (pmmg_graph.hip)
   int edge_hash = 1;      // the edge table's slot: 1 a run of slots per low vertex first, 0 a mix of the whole
                           // key (PMMG_HIP_EDGEHASH=0; cfg4: 31.0 against 56.0 ms)
   // host mode: the device-built background (adjacency, boundary trias) runs
@@ -859,6 +861,7 @@ void pmmg_hip_destroy(pmmg_hip_ctx *c) {
   release(c->o_tet4);
   pmmg_snap_cache_free(&c->snap_cache);
   pmmg_stats_cache_free(&c->stats_cache);
+  pmmg_graph_cache_free(&c->graph_cache);
   for (auto &k : c->kept) {
     release(k.xyz);
     release(k.met);
@@ -2343,6 +2346,7 @@ int pmmg_hip_release_scratch(pmmg_hip_ctx *c) {
   if (c->stream3) HIPCK(c, hipStreamSynchronize(c->stream3));
   pmmg_snap_cache_free(&c->snap_cache);
   pmmg_stats_cache_free(&c->stats_cache);
+  pmmg_graph_cache_free(&c->graph_cache);
   for (DevBuf *b : {&c->bvals2, &c->rs_hist, &c->rs_csum, &c->start_tab}) release(*b);
   c->start_valid = false; // (the next call with a point map builds the start tables again)
   for (pmmg_hip_ctx *l : c->lanes) pmmg_hip_destroy(l);
@@ -2627,6 +2631,40 @@ int pmmg_hip_compute_wgt_faces(pmmg_hip_ctx *c, int np, const double *xyz, const
     return 0;
   }
   return 1;
+}
+
+int pmmg_hip_metis_graph(pmmg_hip_ctx *c, int np, const double *xyz, int ne, const int *tetv, const int *adja,
+                         const int *tet8, int met_size, const double *met, int cap, int64_t *nadjncy, int *xadj,
+                         int *adjncy, int *adjwgt) {
+  if (!c) return 0;
+  HIPCK(c, hipSetDevice(c->device));
+  if (!snap_join(c)) return 0;
+  const bool packed = tet8 != nullptr, wgt = adjwgt != nullptr;
+  if (np < 0 || ne < 0 || !nadjncy || !xadj || cap < 0 || (cap > 0 && !adjncy) ||
+      (ne > 0 && !packed && !tetv && (!adja || wgt)) ||
+      (wgt && ne > 0 && (np < 1 || !xyz || (met_size != 0 && met_size != 1 && met_size != 6) || (met_size && !met)))) {
+    set_err(c, "metis_graph: invalid arguments (np=%d ne=%d met_size=%d cap=%d)", np, ne, met_size, cap);
+    return 0;
+  }
+  if (ne >= (1 << 29)) {
+    set_err(c, "metis_graph: %d tetra exceed the 4*k+i adjacency encoding (2^29)", ne);
+    return 0;
+  }
+  const int *t0 = packed ? tet8 : tetv, *a0 = packed ? tet8 + 4 : adja;
+  if (ne > 0 && (!aligned16(t0) || !aligned16(a0) || (wgt && (((uintptr_t)xyz & 7) || ((uintptr_t)met & 7))))) {
+    set_err(c, "metis_graph: device tetra arrays must be 16-byte, xyz / met 8-byte aligned");
+    return 0;
+  }
+  if (((uintptr_t)xadj & 3) || ((uintptr_t)adjncy & 3) || ((uintptr_t)adjwgt & 3)) {
+    set_err(c, "metis_graph: xadj / adjncy / adjwgt must be 4-byte aligned");
+    return 0;
+  }
+  if (ne > 0 && !a0 && np < 1) {
+    set_err(c, "metis_graph: invalid arguments (np=%d: the adjacency is built from tetv)", np);
+    return 0;
+  }
+  return pmmg_graph_metis(c->stream, np, xyz, ne, t0, packed ? 2 : 1, a0, packed ? 2 : 1, wgt ? 1 : 0, met_size, met,
+                          cap, nadjncy, xadj, adjncy, adjwgt, &c->graph_cache, &c->snap_cache, c->err, sizeof(c->err));
 }
 
 int pmmg_hip_build_boundary(pmmg_hip_ctx *c, int np, int ne, const int *tet8, const int *tetv, const int *adja,

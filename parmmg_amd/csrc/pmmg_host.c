@@ -248,3 +248,73 @@ int pmmg_interp_metrics_and_fields_carry(pmmg_hip_ctx *ctx, int ngrp, const pmmg
                                          pmmg_hip_stats *stats) {
   return interp_groups(ctx, ngrp, old, grp, input_met, 1, carried, src, NULL, stats);
 }
+
+/* ---------------------------------------------------------------- METIS element graph */
+
+void pmmg_host_free(void *p) { free(p); }
+
+int pmmg_graph_mesh_elts2metis(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne, const int *tetv, const int *adja,
+                               int met_size, const double *met, int want_wgt, int **xadj, int **adjncy, int **adjwgt,
+                               int64_t *nadjncy) {
+  if (!ctx) {
+    fprintf(stderr, "[parmmg_host] no HIP context: the element graph has no CPU fallback\n");
+    return 0;
+  }
+  if (!xadj || !adjncy || !adjwgt || !nadjncy || np < 0 || ne < 0 || (ne > 0 && !tetv) ||
+      (want_wgt && ne > 0 && !xyz) || ne >= (1 << 29))
+    return 0;
+  *xadj = *adjncy = *adjwgt = NULL;
+  *nadjncy = 0;
+  if (!met) met_size = 0; /* no metric: PMMG_computeWgt gives PMMG_WGTVAL_HUGEINT */
+  const int wgt = want_wgt != 0;
+  const int64_t cap = 4 * (int64_t)ne; /* device arrays for every face; the host ones are sized from the count */
+  void *d_xyz = NULL, *d_tetv = NULL, *d_adja = NULL, *d_met = NULL, *d_xadj = NULL, *d_adj = NULL, *d_wgt = NULL;
+  int *h_xadj = NULL, *h_adj = NULL, *h_wgt = NULL;
+  int ok = 1;
+#define UP(dst, src, bytes)                                                                    \
+  do {                                                                                         \
+    if (ok && (bytes) > 0) {                                                                   \
+      (dst) = pmmg_hip_malloc(ctx, (int64_t)(bytes));                                          \
+      ok = (dst) != NULL && pmmg_hip_memcpy_h2d(ctx, (dst), (src), (int64_t)(bytes));          \
+    }                                                                                          \
+  } while (0)
+  UP(d_tetv, tetv, sizeof(int) * 4 * (size_t)ne);
+  if (adja) UP(d_adja, adja, sizeof(int) * 4 * (size_t)ne);
+  if (wgt) {
+    UP(d_xyz, xyz, sizeof(double) * 3 * (size_t)np);
+    if (met_size) UP(d_met, met, sizeof(double) * (size_t)met_size * (size_t)np);
+  }
+#undef UP
+  if (ok) ok = (d_xadj = pmmg_hip_malloc(ctx, (int64_t)sizeof(int) * ((int64_t)ne + 1))) != NULL;
+  if (ok) ok = (d_adj = pmmg_hip_malloc(ctx, (int64_t)sizeof(int) * cap)) != NULL;
+  if (ok && wgt) ok = (d_wgt = pmmg_hip_malloc(ctx, (int64_t)sizeof(int) * cap)) != NULL;
+  int64_t n = 0;
+  if (ok)
+    ok = pmmg_hip_metis_graph(ctx, np, (const double *)d_xyz, ne, (const int *)d_tetv, (const int *)d_adja, NULL,
+                              met_size, (const double *)d_met, (int)cap, &n, (int *)d_xadj, (int *)d_adj,
+                              (int *)d_wgt);
+  if (ok) {
+    /* (the reference allocates one entry more than the count, src/metis_pmmg.c:783: never empty) */
+    h_xadj = (int *)malloc(sizeof(int) * ((size_t)ne + 1));
+    h_adj = (int *)calloc((size_t)n + 1, sizeof(int));
+    if (wgt) h_wgt = (int *)calloc((size_t)n + 1, sizeof(int));
+    ok = h_xadj && h_adj && (!wgt || h_wgt) &&
+         pmmg_hip_memcpy_d2h(ctx, h_xadj, d_xadj, (int64_t)sizeof(int) * ((int64_t)ne + 1)) &&
+         pmmg_hip_memcpy_d2h(ctx, h_adj, d_adj, (int64_t)sizeof(int) * n) &&
+         (!wgt || pmmg_hip_memcpy_d2h(ctx, h_wgt, d_wgt, (int64_t)sizeof(int) * n));
+  }
+  void *dev[] = {d_xyz, d_tetv, d_adja, d_met, d_xadj, d_adj, d_wgt};
+  for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++)
+    if (dev[i]) pmmg_hip_free(ctx, dev[i]);
+  if (!ok) {
+    free(h_xadj);
+    free(h_adj);
+    free(h_wgt);
+    return 0;
+  }
+  *xadj = h_xadj;
+  *adjncy = h_adj;
+  *adjwgt = h_wgt;
+  *nadjncy = n;
+  return 1;
+}

@@ -117,6 +117,23 @@ int pmmg_interp_metrics_and_fields_carry(pmmg_hip_ctx *ctx, int ngrp, const pmmg
 int pmmg_interp_metrics_and_fields_map(pmmg_hip_ctx *ctx, int ngrp, const pmmg_old_group *old, pmmg_new_group *grp,
                                        int input_met, const int *const *src, pmmg_hip_stats *stats);
 
+/* ---- The METIS element graph of a group -----------------------------------
+ * PMMG_graph_meshElts2metis (src/metis_pmmg.c:746-823) from host arrays in the
+ * "row r = entity r+1" layout, through pmmg_hip_metis_graph: the arrays that
+ * are not on the device go up, the graph is built there, and xadj[ne+1],
+ * adjncy and adjwgt come back in arrays this call allocates (sized from the
+ * entry count, one entry more as in the reference; release them with
+ * pmmg_host_free).  adja NULL: the adjacency is built on the device
+ * (MMG3D_hashTetra's branch, :756).  As in the reference, want_wgt == 0
+ * leaves *adjwgt NULL (distribution, last iteration: :790; xyz and met are
+ * not read), and weights without a metric (met NULL) are all
+ * PMMG_WGTVAL_HUGEINT.  *nadjncy receives the entry count xadj[ne].  Returns
+ * 1, or 0 (nothing allocated; the reason in pmmg_hip_last_error). */
+int pmmg_graph_mesh_elts2metis(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne, const int *tetv, const int *adja,
+                               int met_size, const double *met, int want_wgt, int **xadj, int **adjncy, int **adjwgt,
+                               int64_t *nadjncy);
+void pmmg_host_free(void *p);
+
 /* ---- halo shards of a background group (pmmg_shard.c) ----
  * All arrays in the "row r = entity r+1" layout of parmmg_hip.h. */
 

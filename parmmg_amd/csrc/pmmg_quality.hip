@@ -136,28 +136,8 @@ __global__ __launch_bounds__(kQBlock) void k_tetra_qual(const double *xyz, int n
 // not modelled), the load-balancing weight of the faces on parallel
 // interfaces.  Same operation order as oracle/pmmg_oracle.c orc_face_wgt;
 // exp / log1p are the device library's (within an ulp of the host's).
-constexpr double kHugeWgt = 1000000.0; // PMMG_WGTVAL_HUGEINT
-// (lenedg_iso / lenedg_ani and MMG5_EPS: pmmg_quality.hpp, shared with pmmg_meshstats.hip)
-__constant__ int kIare[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}}; // MMG5_iare
-__constant__ int kIarf[4][3] = {{5, 4, 3}, {5, 1, 2}, {4, 2, 0}, {3, 0, 1}};     // MMG5_iarf
-
-__device__ double face_wgt(const double *xyz, const int *v, int ifac, int met_size, const double *met) {
-  if (met_size != 1 && met_size != 6) return kHugeWgt;
-  double res = 0.0;
-  for (int i = 0; i < 3; i++) {
-    const int ia = kIarf[ifac][i];
-    const int ip1 = v[kIare[ia][0]], ip2 = v[kIare[ia][1]];
-    const double *ca = xyz + 3 * (size_t)(ip1 - 1), *cb = xyz + 3 * (size_t)(ip2 - 1);
-    const double len = met_size == 1 ? lenedg_iso(ca, cb, met[ip1 - 1], met[ip2 - 1])
-                                     : lenedg_ani(ca, cb, met + 6 * (size_t)(ip1 - 1), met + 6 * (size_t)(ip2 - 1));
-    if (len <= 1.0)
-      res += len - 1.0;
-    else
-      res += 1.0 / len - 1.0;
-  }
-  const double w = 1.0 / exp(28.0 * res / 3.0);
-  return w < kHugeWgt ? w : kHugeWgt;
-}
+// (face_wgt, its MMG5_iare / MMG5_iarf tables, lenedg_iso / lenedg_ani and MMG5_EPS: pmmg_quality.hpp, shared with
+// pmmg_meshstats.hip and pmmg_graph.hip)
 
 // PMMG_computeWgt_mesh: qual[k] = sum over the faces of k tagged `tag` of the
 // face weight, for used tetra with an xtetra; the others keep qual[k]

@@ -313,7 +313,7 @@ class TransferContext:
 
     def release_scratch(self) -> None:
         """pmmg_hip_release_scratch: free the snapshot buckets, the binning's
-        scratch, the reports' edge table and the group lanes (re-allocated on
+        scratch, the reports' edge table, the element graph's scratch and the group lanes (re-allocated on
         demand)."""
         self._ck(self.lib.pmmg_hip_release_scratch(self.h), "release_scratch")
 
@@ -402,6 +402,38 @@ class TransferContext:
                                                      0 if met is None else int(met.shape[1]), _p(met), _p(wgt)),
                  "compute_wgt_faces")
         return wgt
+
+    def metis_graph(self, xyz, tetv, adja=None, tet8=None, met=None, weights=True, cap=None, out=None):
+        """PMMG_graph_meshElts2metis on the device (pmmg_hip_metis_graph):
+        device arrays.  Tetra from tet8 ([ne, 8] packed records) when given,
+        else from tetv + adja; with neither adja nor tet8 the adjacency is
+        built on the device first.  weights=False: the unweighted graph (xyz
+        and met are not read and may be None); weights without a metric are
+        all PMMG_WGTVAL_HUGEINT.  Returns (xadj [ne + 1], adjncy [n], adjwgt
+        [n] | None) DeviceArrays, n = xadj[ne]; cap: rows to allocate for the
+        lists (None: 4 ne, one per face); out = (xadj, adjncy, adjwgt) arrays
+        to fill instead of new ones."""
+        given = [a for a in (xyz, tetv, adja, tet8, met) if a is not None]
+        if not all(_is_dev(a) for a in given):
+            raise ValueError("metis_graph takes device arrays")
+        ne = (tet8 if tet8 is not None else tetv).shape[0]
+        cap = 4 * ne if cap is None else int(cap)
+        if out is not None:
+            xadj, adjncy, adjwgt = out
+        else:
+            xadj = self.empty((ne + 1,), np.int32)
+            adjncy = self.empty((cap,), np.int32)
+            adjwgt = self.empty((cap,), np.int32) if weights else None
+        n = ctypes.c_int64(0)
+        self._ck(self.lib.pmmg_hip_metis_graph(self.h, 0 if xyz is None else xyz.shape[0], _p(xyz), ne, _p(tetv),
+                                               _p(adja), _p(tet8), 0 if met is None else int(met.shape[1]), _p(met),
+                                               cap, ctypes.byref(n), _p(xadj), _p(adjncy),
+                                               _p(adjwgt) if weights else None), "metis_graph")
+        if out is None:
+            for a in (adjncy, adjwgt):
+                if a is not None:
+                    a.shape, a.nbytes = (n.value,), 4 * n.value
+        return xadj, adjncy, (adjwgt if weights else None)
 
     # ------------------------------------------------------------------ split over GPUs (RCCL)
     @staticmethod

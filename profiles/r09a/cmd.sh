@@ -1,0 +1,18 @@
+# r09a: the GPU visits of the element-graph change (each block one visit, every GPU step under its own time limit)
+set -o pipefail
+# 1. the new tests
+timeout -k 10 400 python3 -m pytest tests/test_gpu_metis_graph.py -m gpu -x -q -s --durations=8
+# 2. the timing tool on cfg2, then cfg4
+timeout -k 10 200 python3 -u tools/metis_graph_time.py --config cfg2 --out bench_out/r09a/metis_graph_cfg2.json && \
+timeout -k 10 900 python3 -u tools/metis_graph_time.py --config cfg4 --out bench_out/r09a/metis_graph_cfg4.json
+# 3. the whole GPU suite, then smoke()
+timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -q && \
+timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()"
+# 4. bench.py of the parent commit's tree (exported and built beside this one as _ab/parent) and of this tree, alternating
+for i in 1 2 3 4; do
+  (cd _ab/parent && timeout -k 10 400 python3 -u bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline) && \
+  timeout -k 10 400 python3 -u bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline || break
+done
+# resource usage (no GPU): the flags of parmmg_amd/build.py plus -Rpass-analysis=kernel-resource-usage
+SRC=pmmg_graph.hip bash tools/resource_usage.sh k_graph
+SRC=pmmg_quality.hip bash tools/resource_usage.sh k_wgt

@@ -2,12 +2,13 @@
 # Per-kernel VGPRs / scratch / occupancy / LDS of the HIP module, from the
 # compiler's resource-usage remarks (same flags as parmmg_amd/build.py).
 #   bash tools/resource_usage.sh [kernel-name-regex]
+# SRC=pmmg_graph.hip (or another translation unit of parmmg_amd/csrc) instead of pmmg_hip.hip
 set -o pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$(mktemp -d)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -mllvm -amdgpu-sched-strategy=max-memory-clause -std=c++17 \
   -ffp-contract=off -fPIC -c --offload-device-only -Rpass-analysis=kernel-resource-usage ${EXTRA_FLAGS} \
-  -I"$ROOT/include" -o "$OUT/hip.o" "$ROOT/parmmg_amd/csrc/pmmg_hip.hip" 2> "$OUT/usage.txt"
+  -I"$ROOT/include" -o "$OUT/hip.o" "$ROOT/parmmg_amd/csrc/${SRC:-pmmg_hip.hip}" 2> "$OUT/usage.txt"
 python3 - "$OUT/usage.txt" "${1:-.}" <<'PY'
 import re, sys, subprocess
 pat = re.compile(sys.argv[2])
