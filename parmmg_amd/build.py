@@ -25,9 +25,6 @@ INC = os.path.join(ROOT, "include")
 ORACLE = os.path.join(ROOT, "oracle")
 
 HIP_SO = os.path.join(PKG, "libpmmg_hip.so")
-# the measurement build (-DPMMG_HIP_MEASURE: the A/B switches of tools/, never
-# linked by the host layer or loaded by the tests; PMMG_HIP_SO selects it)
-HIP_MEASURE_SO = os.path.join(PKG, "libpmmg_hip_measure.so")
 HOST_SO = os.path.join(PKG, "libpmmg_host.so")
 SYNTH_SO = os.path.join(PKG, "libpmmg_synth.so")
 ORACLE_SO = os.path.join(ORACLE, "liboracle.so")
@@ -57,8 +54,8 @@ def _stale(out: str, deps: list[str]) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_hip(force: bool = False, measure: bool = False) -> str:
-    out = HIP_MEASURE_SO if measure else HIP_SO
+def build_hip(force: bool = False) -> str:
+    out = HIP_SO
     src = os.path.join(CSRC, "pmmg_hip.hip")
     snap = os.path.join(CSRC, "pmmg_snapshot.hip")
     qual = os.path.join(CSRC, "pmmg_quality.hip")
@@ -67,16 +64,14 @@ def build_hip(force: bool = False, measure: bool = False) -> str:
     deps = [src, snap, qual, mstats, graph, os.path.join(INC, "parmmg_hip.h"), __file__] + [
         os.path.join(CSRC, h) for h in ("pmmg_device.hpp", "pmmg_prep.hpp", "pmmg_vol.hpp", "pmmg_bdy.hpp",
                                         "pmmg_fallback.hpp", "pmmg_snapshot.hpp", "pmmg_quality.hpp",
-                                        "pmmg_meshstats.hpp", "pmmg_graph.hpp",
-                                        "pmmg_brick.hpp", "pmmg_sort.hpp")]
+                                        "pmmg_meshstats.hpp", "pmmg_graph.hpp", "pmmg_sort.hpp")]
     if force or _stale(out, deps):
         # max-memory-clause scheduling: the gathers of a step issued as clauses
         # (volume kernel -4.6 % at cfg4, same registers; profiles/r02e/sweep_sched_strategy.txt)
         _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-mllvm", "-amdgpu-sched-strategy=max-memory-clause",
               "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
               # (r05: flowing off a lambda that a `return 0` made non-void is undefined: a host segfault)
-              "-Werror=return-type"] + (["-DPMMG_HIP_MEASURE"] if measure else []) +
-             [f"-I{INC}", "-o", out, src, snap, qual, mstats, graph])
+              "-Werror=return-type", f"-I{INC}", "-o", out, src, snap, qual, mstats, graph])
     return out
 
 
@@ -128,12 +123,7 @@ def build_c_test(force: bool = False) -> str:
 
 
 def build_all(force: bool = False) -> None:
-    from concurrent.futures import ThreadPoolExecutor
-
-    with ThreadPoolExecutor(2) as ex:  # the two HIP builds side by side (hipcc is single-threaded)
-        jobs = [ex.submit(build_hip, force), ex.submit(build_hip, force, True)]
-        for j in jobs:
-            j.result()
+    build_hip(force)
     build_host(force)
     build_synth(force)
     build_oracle(force)

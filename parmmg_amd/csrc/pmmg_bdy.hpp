@@ -13,7 +13,7 @@ namespace pmmg {
 __device__ __forceinline__ int bdy_query(const Bg &bg, const Frame *fr, const unsigned long long *sgrid, int gs,
                                          const double *qxyz,
                                          int ip, const Slots &S, int *elem_out, int8_t *hit_out, int maxstep,
-                                         int &steps, int &scans, int k0, bool interp = true) {
+                                         int &steps, int &scans, int k0) {
   int hit = 0;
   double x[3];
   load_pt(qxyz, ip, x);
@@ -107,7 +107,7 @@ __device__ __forceinline__ int bdy_query(const Bg &bg, const Frame *fr, const un
     k = next;
   }
   if (hit) {
-    if (interp) interp_bdy(S, ip, t.v, phi, edge, vertex);
+    interp_bdy(S, ip, t.v, phi, edge, vertex);
     if (elem_out) elem_out[ip - 1] = k;
     if (hit_out) hit_out[ip - 1] = (int8_t)(hit | ((vertex >= 0 ? vertex : (edge >= 0 ? edge : 0)) << 4));
   }
@@ -115,9 +115,8 @@ __device__ __forceinline__ int bdy_query(const Bg &bg, const Frame *fr, const un
 }
 
 // One lane per surface query, the static XCD-chunked split of the grid
-// (default), or (dyn, PMMG_HIP_BDYDYN=1) every wave claiming the next 64
-// queries of its XCD's eighth from a counter: measured, the claiming waves
-// slowed the volume kernel beside them (profiles/r03y).
+// (r03y: every wave claiming the next 64 queries of its XCD's eighth from a
+// counter slowed the volume kernel beside it).
 // (r05: a register budget for 5 or 6 waves per SIMD instead of the compiler's
 // 4: the step +-0 / +2 %, the 8-way rank's surface branch +-0, profiles/r05ak)
 // MAP = 1 (a call with a point map): a query whose source vertex has a start
@@ -126,47 +125,26 @@ template <int MAP = 0>
 __global__ __launch_bounds__(kBlock) void k_bdy(Bg bg, const Frame *fr, const unsigned long long *sgrid, int gs,
                                                 const double *qxyz,
                                                 const int *order, Slots S, int *elem_out, int8_t *hit_out, int *fb,
-                                                DevStats *st, int maxstep, int dyn, FbInit fi, FbGridBufs gb,
-                                                const int *gate, int want, unsigned long long *wt, MapArgs ma) {
-  if (want >= 0 && gate[0] != want) return; // (one of the two orders' launches, as k_vol)
-#ifdef PMMG_HIP_MEASURE
-  // measurement build, PMMG_HIP_WAVETIME=1: per wave {start, end, longest walk, active lanes} (wall clock)
-  const unsigned long long wt0 = wt ? wall_clock64() : 0ULL;
-  unsigned wt_steps = 0, wt_act = 0;
-#endif
+                                                DevStats *st, int maxstep, FbInit fi, FbGridBufs gb, MapArgs ma) {
   __shared__ BlockStats bs;
   bstats_init(&bs);
   __syncthreads();
-  const long long n = st->nbdy;
-  const int x = blockIdx.x & 7;
-  const long long lo = n * x / 8, hi = n * (x + 1) / 8;
-  const XcdChunk ch = xcd_chunk(n); // static split (dyn == 0)
-  for (int it = 0;; it++) {
-    long long i;
-    if (dyn & 1) {
-      int base = 0;
-      if (__lane_id() == 0) base = atomicAdd(&st->bdy_next[x], 64);
-      base = __shfl(base, 0);
-      if (lo + base >= hi) break;
-      i = lo + base + __lane_id();
-    } else {
-      if (it >= ch.iters) break;
-      i = ch.start + it * ch.stride;
-    }
-    const bool active = i < ((dyn & 1) ? hi : ch.hi);
+  const XcdChunk ch = xcd_chunk(st->nbdy);
+  for (int it = 0; it < ch.iters; it++) {
+    const long long i = ch.start + it * ch.stride;
+    // (a compiler barrier: without it the loads that do not change from round to round — frame, slots — are
+    // hoisted out of the loop and stay in registers over the walk and the interpolation: 129 / 132 VGPRs
+    // instead of 119 / 121, 3 waves per SIMD instead of 4; there is one round for up to 1M surface points)
+    asm volatile("" ::: "memory");
+    const bool active = i < ch.hi;
     int steps = 0, hit = 0, ip = 0, scans = 0, k0 = 0;
     if (active) {
       ip = order[i];
       if constexpr (MAP != 0) k0 = map_start(ma.src, ma.start_tri, bg.np, bg.nt, ip, false);
-      // (measurement build, dyn bit 1 = PMMG_HIP_BDYNOINTERP=1: the walks without the interpolation; r06w:
-      // the interpolation is ~half of a surface wave's lifetime.  r06x: a cooperative version — the three
-      // vertices' rows gathered by the wave through LDS, 8-byte pieces — made the waves longer, 32 vs 30 us,
-      // and the step +27 us: not kept)
-#ifdef PMMG_HIP_MEASURE
-      hit = bdy_query(bg, fr, sgrid, gs, qxyz, ip, S, elem_out, hit_out, maxstep, steps, scans, k0, !(dyn & 2));
-#else
+      // (r06w: the interpolation is ~half of a surface wave's lifetime.  r06x: a cooperative version — the
+      // three vertices' rows gathered by the wave through LDS, 8-byte pieces — made the waves longer, 32 vs
+      // 30 us, and the step +27 us: not kept)
       hit = bdy_query(bg, fr, sgrid, gs, qxyz, ip, S, elem_out, hit_out, maxstep, steps, scans, k0);
-#endif
     }
     wave_count(&bs, kCntFanScan, active && scans > 0);
     if constexpr (MAP != 0) wave_count(&bs, kCntBdySrc, active && k0 != 0);
@@ -176,24 +154,7 @@ __global__ __launch_bounds__(kBlock) void k_bdy(Bg bg, const Frame *fr, const un
       fi.at(slot);
     }
     wave_stats(&bs, active, hit, steps);
-#ifdef PMMG_HIP_MEASURE
-    if (wt) {
-      unsigned m = active ? (unsigned)steps : 0u;
-      for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-      wt_steps = max(wt_steps, m);
-      wt_act += (unsigned)__popcll(__ballot(active));
-    }
-#endif
   }
-#ifdef PMMG_HIP_MEASURE
-  if (wt && __lane_id() == 0) {
-    unsigned long long *w = wt + 4 * (size_t)(blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64);
-    w[0] = wt0;
-    w[1] = wall_clock64();
-    w[2] = wt_steps;
-    w[3] = wt_act;
-  }
-#endif
   __syncthreads();
   bstats_flush(&bs, st);
   // (the surface fallback list's query grid: k_fb_grid, launched next)

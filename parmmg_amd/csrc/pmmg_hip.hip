@@ -4,7 +4,7 @@
 // Replaces, behind the C-ABI of include/parmmg_hip.h, the per-group body of
 // PMMG_interpMetricsAndFields (reference src/interpmesh_pmmg.c:477-741):
 //   PMMG_locatePointVol      src/locate_pmmg.c:786-883     -> k_vol<layout> (fp32 filter walk + exact
-//                                                             acceptance + interpolation), k_vol_walk_exact
+//                                                             acceptance and continuation + interpolation)
 //   PMMG_interp4bar_*        src/interpmesh_pmmg.c:206-270 -> vol_slot / vol_interp_packed in k_vol (pmmg_vol.hpp)
 //   PMMG_locatePointBdy      src/locate_pmmg.c:587-723     -> k_bdy (locate + interpolate)  (pmmg_bdy.hpp)
 //   exhaustive / closest     src/locate_pmmg.c:477-515, 737-770 -> k_*_exhaust_accept, k_*_exhaust_closest
@@ -15,16 +15,16 @@
 // pmmg_prep.hpp.
 //
 // Pipeline of one pmmg_hip_locate_interp (no host synchronisation inside):
-//   main stream     reset, coherence test, frame, volume seeds | query order
-//                   (Morton bins or stable class compaction, chosen on the
-//                   device) | fp32 filter walk + exact acceptance | exact
-//                   continuation | interpolation | join | fallbacks
-//   surface stream  (after the order) surface seeds, node->tria CSR, k_bdy
+//   main stream     reset, coherence test, frame, volume seeds | volume
+//                   kernel (fp32 filter walk, exact acceptance and
+//                   continuation, interpolation) | fallbacks | join
+//   surface stream  the query order's lists (stable class compaction, or the
+//                   Morton bins on a stream of their own), surface seeds,
+//                   k_bdy, its fallbacks
+// (the order is forced, or decided on the device by the coherence test and
+// read back once by a large call: run_device)
 #include <hip/hip_ext.h> // hipExtLaunchKernelGGL: events recorded by the kernel dispatch itself
 #include <hip/hip_runtime.h>
-#ifdef PMMG_HIP_MEASURE
-#include <rocprim/device/device_radix_sort.hpp> // the brick renumbering's sort (measurement build)
-#endif
 
 #include <math.h>
 #include <stdarg.h>
@@ -45,9 +45,6 @@
 
 #include "pmmg_device.hpp"
 #include "pmmg_prep.hpp"
-#ifdef PMMG_HIP_MEASURE
-#include "pmmg_brick.hpp" // measurement build only
-#endif
 #include "pmmg_sort.hpp"
 #include "pmmg_vol.hpp"
 #include "pmmg_bdy.hpp"
@@ -65,13 +62,7 @@ namespace {
 // ---------------------------------------------------------------- slot layouts
 
 typedef void (*VolFn)(Bg, const Frame *, const unsigned long long *, int, const double *, const uint8_t *,
-                      const int *, const double *, int, ContEntry *, DevStats *, Slots, int *, int8_t *, int,
-                      const int *, int, int, int, LocBuf, int, ContArgs, MapArgs);
-typedef void (*InterpFn)(LocBuf, const int *, const DevStats *, int, Slots, const int *, int, int, int);
-
-// the split stage's walk kernel: the locate-only layout, writing located records
-constexpr VolFn kVolWalk = k_vol<0, 0, 0, 0, 0, 0, 0>;
-constexpr VolFn kVolWalkMap = k_vol<0, 0, 0, 0, 0, 0, 0, 1>; // (a call with a point map)
+                      const int *, int, DevStats *, Slots, int *, int8_t *, int, const int *, int, ContArgs, MapArgs);
 
 struct LayoutEntry {
   int c[6];
@@ -79,7 +70,6 @@ struct LayoutEntry {
   VolFn fn_packed;  // packed per-vertex records, one pass (null: layout not packable)
   VolFn fn_packed2; // the same in two passes over the record halves (null: not splittable)
   VolFn map_fn, map_fn_packed, map_fn_packed2; // the same three for a call with a point map (k_vol's MAP)
-  InterpFn ifn, ifn_packed, ifn_packed2; // the split stage's interpolation kernels, same three forms
 };
 
 template <int NP, int A, int B, int C, int D, int E, int F, int MAP = 0>
@@ -88,18 +78,10 @@ constexpr VolFn packed_fn() {
   if constexpr (L::valid() && L::passes_ok(NP)) return k_vol<NP, A, B, C, D, E, F, MAP>;
   else return nullptr;
 }
-template <int NP, int A, int B, int C, int D, int E, int F>
-constexpr InterpFn packed_ifn() {
-  using L = PackedLayout<A, B, C, D, E, F>;
-  if constexpr (L::valid() && L::passes_ok(NP)) return k_vol_interp<NP, A, B, C, D, E, F>;
-  else return nullptr;
-}
-
 #define PMMG_LAYOUT(a, b, c, d, e, f)                                                                    \
   {{a, b, c, d, e, f}, k_vol<0, a, b, c, d, e, f>, packed_fn<1, a, b, c, d, e, f>(),                    \
    packed_fn<2, a, b, c, d, e, f>(), k_vol<0, a, b, c, d, e, f, 1>, packed_fn<1, a, b, c, d, e, f, 1>(), \
-   packed_fn<2, a, b, c, d, e, f, 1>(), k_vol_interp<0, a, b, c, d, e, f>, packed_ifn<1, a, b, c, d, e, f>(), \
-   packed_ifn<2, a, b, c, d, e, f>()}
+   packed_fn<2, a, b, c, d, e, f, 1>()}
 // common slot layouts (metric first): aniso metric + scalar/vector/tensor
 // (BASELINE cfg3/cfg4, libexamples cube-solphys.sol), iso metric + scalars
 // (cfg2, cfg5), metric only; anything else runs the runtime-layout variant
@@ -115,11 +97,7 @@ const LayoutEntry kLayouts[] = {
 // layout allows only it; 0 = by the record's size: two above 8 doubles, where
 // one pass holds the whole record in registers — cfg4's 16 doubles: 168
 // VGPRs, 3 waves per SIMD, 4.42 ms per step against 4.18 in two passes, r05d)
-struct VolPick {
-  VolFn fn;     // the fused kernel (walk + exact test + interpolation)
-  InterpFn ifn; // the split stage's interpolation kernel (after kVolWalk)
-};
-VolPick pick_layout(const Slots &S, int passes = 0, bool map = false) {
+VolFn pick_layout(const Slots &S, int passes = 0, bool map = false) {
   for (const LayoutEntry &e : kLayouts) {
     int n = 0;
     while (n < 6 && e.c[n] > 0) n++;
@@ -127,21 +105,19 @@ VolPick pick_layout(const Slots &S, int passes = 0, bool map = false) {
     bool ok = true;
     for (int j = 0; j < n; j++) ok = ok && (S.s[j].code == e.c[j]);
     if (!ok) continue;
-    if (!S.rec) return {map ? e.map_fn : e.fn, e.ifn};
+    if (!S.rec) return map ? e.map_fn : e.fn;
     if (passes == 0) {
       int k = 0;
       for (int j = 0; j < n; j++) k += e.c[j];
       passes = k > 8 ? 2 : 1;
     }
     const VolFn p1 = map ? e.map_fn_packed : e.fn_packed, p2 = map ? e.map_fn_packed2 : e.fn_packed2;
-    VolFn a = passes == 2 ? p2 : p1, b = passes == 2 ? p1 : p2;
-    InterpFn ia = passes == 2 ? e.ifn_packed2 : e.ifn_packed, ib = passes == 2 ? e.ifn_packed : e.ifn_packed2;
-    return {a ? a : b, ia ? ia : ib};
+    const VolFn a = passes == 2 ? p2 : p1, b = passes == 2 ? p1 : p2;
+    return a ? a : b;
   }
-  if (S.rec) return {nullptr, nullptr};
-  return {map ? k_vol<0, -1, 0, 0, 0, 0, 0, 1> : k_vol<0, -1, 0, 0, 0, 0, 0>, k_vol_interp<0, -1, 0, 0, 0, 0, 0>};
+  if (S.rec) return nullptr;
+  return map ? k_vol<0, -1, 0, 0, 0, 0, 0, 1> : k_vol<0, -1, 0, 0, 0, 0, 0>;
 }
-
 
 // the slot layouts the packed-record interpolation is compiled for
 bool packed_supported(int met_size, int nfield, const int *fsize) {
@@ -149,19 +125,8 @@ bool packed_supported(int met_size, int nfield, const int *fsize) {
   S.rec = reinterpret_cast<const double *>(16);
   if (met_size) S.s[S.n++].code = met_size;
   for (int j = 0; j < nfield && S.n < kMaxSlot; j++) S.s[S.n++].code = fsize[j];
-  return pick_layout(S).fn != nullptr;
+  return pick_layout(S) != nullptr;
 }
-
-#ifdef PMMG_HIP_MEASURE
-// measurement build, PMMG_HIP_SETORDER=1: the query order also written to
-// the stats by a one-thread kernel on the main stream, as up to r03ad (the
-// volume kernel now takes it as an argument: one launch less between the seed
-// grid and the volume kernel)
-__global__ void k_set_order(DevStats *st, int sorted, int bits) {
-  st->sorted = sorted;
-  st->bin_bits = bits;
-}
-#endif
 
 } // namespace
 
@@ -173,8 +138,8 @@ struct DevBuf {
 };
 
 enum {
-  EV_START, EV_FRAME, EV_PREP, EV_ORDER, EV_VOL0, EV_WALK, EV_VOL, EV_JOIN, EV_END, EV_BDY0, EV_BDY1, EV_RESET,
-  EV_SB0, EV_ORDER2, EV_SRFSEED, EV_FILL, EV_BDYFB, EV_QUANT, EV_COUNT
+  EV_START, EV_FRAME, EV_PREP, EV_ORDER, EV_VOL0, EV_WALK, EV_JOIN, EV_END, EV_BDY0, EV_BDY1, EV_RESET,
+  EV_SB0, EV_ORDER2, EV_FILL, EV_COUNT
 };
 
 struct pmmg_hip_ctx {
@@ -182,12 +147,11 @@ struct pmmg_hip_ctx {
   int options = 0;
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr; // surface branch, concurrent with the volume walk
-  hipStream_t stream3 = nullptr; // Morton binning of a call whose order is decided on the device (created at the
-                                 // first such call), beside the input order's surface list on stream2
+  hipStream_t stream3 = nullptr; // Morton binning of a call that may take that order (created at the first such
+                                 // call, not with the context: a context that never bins keeps to two streams),
+                                 // beside the input order's surface list on stream2
   hipStream_t stream_f = nullptr; // a large call's seed-grid refill, right after the volume kernel, beside the
                                   // main stream's tail (created at the first such call)
-  hipStream_t stream2_hi = nullptr; // measurement build, PMMG_HIP_SRFPRIO=1: the same at the highest priority,
-  bool srf_prio = false;            // for calls of >= kSmallGroup queries (see run_device)
   char err[512] = {0};
   Bg bg{};
   int met_size = 0;
@@ -201,26 +165,15 @@ struct pmmg_hip_ctx {
   DevBuf o_xyz, o_tetv, o_adja, o_triv, o_adjt, o_met, o_rec;
   std::vector<DevBuf> o_f;
   // work buffers
-  DevBuf frame, stats, grid, sgrid, order_v, order_b, cont, xq;
+  DevBuf frame, stats, grid, sgrid, order_v, order_b, xq;
   DevBuf cohd;                            // the coherence test's sampled distances (k_bbox)
   DevBuf axh;                             // per-axis histograms of the seed grid map (k_quantize)
   DevBuf bkeys, bkeys2, bvals, bvals2;    // Morton binning: keys and ids, ping-ponged by the radix sort
   DevBuf rs_hist, rs_csum;                // the radix sort's digit table and its scan's chunk sums
-  // PMMG_HIP_BRICK (measurement only, pmmg_brick.hpp): the background renumbered by bricks
-  DevBuf brk_k, brk_k2, brk_v, brk_v2, brk_vinv, brk_tinv, brk_xq, brk_xyz, brk_sol, brk_rec, brk_tmp;
-  int brick = 0;
-  int set_order = 0; // test-only PMMG_HIP_SETORDER=1 (see k_set_order)
-  int no_fb = 0;     // measurement build: PMMG_HIP_NOFB
-  int stream3_mode = 1; // the binning's own stream: 1 created at the first auto-order call, 2 with the context,
-                        // 0 none (measurement build: PMMG_HIP_STREAM3)
-  int srf_solo = -1; // the surface branch waits for the seed grid: -1 in calls of >= kSmallGroup queries (r04zo,
-                     // cfg4: the seed grid ran at 455 instead of 261 us beside k_bdy; step 4.24 -> 4.13 ms,
-                     // Mmg-like 5.01 -> 4.93, shuffled =), 1 always, 0 never (PMMG_HIP_SRFSOLO)
   // the seed grids left clean by the previous call (its last kernels refill
   // them while the other stream finishes): k_reset skips what is clean
   void *grid_clean_p = nullptr, *sgrid_clean_p = nullptr;
   long long grid_clean_n = 0, sgrid_clean_n = 0;
-  DevBuf qs;                              // volume query coordinates in processing order (Morton path)
   DevBuf cls_cnt;                         // per-block class counts (surface list compaction)
   DevBuf oflag;                           // the coherence test's {sorted, bin_bits} on the device
   DevBuf qmin;                               // tetra quality minimum (pmmg_hip_tetra_qual)
@@ -254,41 +207,21 @@ struct pmmg_hip_ctx {
   int snap_ok = 1;
   int verbose = 0; // PMMG_HIP_VERBOSE: host-mode transfer timings on stderr
   int tpc = 8;        // background tetra per volume seed cell (PMMG_HIP_TPC)
-  int seed_lanes = 4;  // sampled tetra per seed run of 4 records (PMMG_HIP_SEEDLANES, 1..4)
-  int seed_v0 = 0;     // measurement build, PMMG_HIP_SEEDV0=1: a sample's first vertex instead of its centroid
   int pack_passes = 0; // packed records gathered in 1 or 2 passes over the record (PMMG_HIP_PACKPASS; 0: by size)
-  int bbox_stride = 64;  // the frame's bbox samples np / n vertices (PMMG_HIP_BBOX; r03o: 64 instead of 16 and
-  int hist_stride = 256; // 256 instead of 64 for the axis histograms: preparation -0.15 ms at cfg4, same walks)
-  int bdy_bpx = 512;     // k_bdy blocks per XCD at most (PMMG_HIP_BDYBPX), in blocks of kBlock threads
-  int bdy_wave = 0;      // k_bdy in one-wave blocks (PMMG_HIP_BDYWAVE)
-  int ev_vol0 = EV_VOL0, ev_vol = EV_VOL; // the events that open / close the call's volume stage (collect_stats)
-  int quant_side = 0;    // a large call's fixed-point copy beside the seed grid (PMMG_HIP_QUANTSIDE)
-  int fuse_cont = 1;     // the exact continuation inside the volume kernel (PMMG_HIP_FUSECONT=0: the list and
-                         // k_vol_walk_exact, as before r06)
-  int host_order = 1;    // a large auto-order call reads the coherence test's decision on the host after k_bbox
-                         // and enqueues that order's kernels only (PMMG_HIP_HOSTORDER=0: both, gated on the
-                         // device, as before r06)
+  int ev_vol0 = EV_VOL0; // the event that opens the call's volume stage (collect_stats; it closes at EV_WALK)
   int *flag_host = nullptr;     // (pinned, coherent: k_bbox's last block writes the decision here too)
   int *flag_host_dev = nullptr; // (its device address)
-  int bdy_dyn = 0;       // k_bdy: waves claim work from per-XCD counters (PMMG_HIP_BDYDYN=1; r03y: the claiming
-                         // waves slowed the volume kernel beside them, 8-way rank 0.70 -> 0.64 ms static)
   int srf_g = 0;         // test-only PMMG_HIP_SRFG: the surface seed grid's cells per axis (1: one seed for all)
   int srf_mult = 8;      // the surface seed grid has srf_mult * nt / 2 cells (PMMG_HIP_SRFMULT; r03r at cfg4: 1 /
                          // 8 / 32 -> 7.4 / 3.9 / 2.7 steps per surface point, surface branch 0.446 / 0.403 /
                          // 0.399 ms: a surface grid sized like a volume grid left ~33 trias per occupied cell)
   int bin_bits = kBinBitsCoherent; // Morton bits per axis of the binning keys when the order is forced (1..7,
                                     // PMMG_HIP_BINBITS; auto mode: the coherence test picks)
-  int bin_qs = 0;       // the binning copies the volume queries' coordinates in processing order (PMMG_HIP_BINQS=1;
-                        // r03: -0.5 ms in the walk on a shuffled numbering, +1 ms in the binning)
   int maxstep = 1024; // longer walks go to the exhaustive kernels (PMMG_HIP_MAXSTEP; the reference caps at ne).
                       // r05: 4096 -> 1024; a walk that long cycles along a concave boundary (carried cfg4
                       // iteration: 2644 queries at the cap, all then accepted by the exhaustive search; the
                       // longest legitimate walk seen is 302 steps, cfgG)
   int fanmax = kFanMax;    // cone fans longer than this take the O(nt) scan (test-only PMMG_HIP_FANMAX)
-  int pad = 0;           // measurement build, PMMG_HIP_PAD: extra VALU / L1 work per walk step (k_vol)
-  int xcd_run = 64;      // k_vol's blocks dealt to the XCDs in runs of 64 (4096 queries) instead of contiguous
-                         // eighths: r04c at cfg4, volume kernel 3.80 -> 3.50 ms, Mmg-like numbering 5.83 -> 4.14 ms
-                         // (measurement build: PMMG_HIP_XCDRUN, 0 = eighths)
   // carry-over (pmmg_hip_keep / pmmg_hip_carry_over): kept[slot] holds the new
   // points and written rows of a host-mode call; an armed carry (carry_slot
   // >= 0) feeds the next host-mode set_background / set_solutions from it
@@ -320,7 +253,8 @@ struct pmmg_hip_ctx {
   // pmmg_hip_locate_interp_groups: lanes[j] is lane j (same device and
   // options, created at the first groups call); lane 0 enqueues on this
   // context's own streams (no extra hardware queue) but has its own state, so
-  // a groups call leaves this context's background and solutions as they were
+  // a groups call leaves this context's background and solutions as they were.
+  // Every other lane has one stream, its surface branch on its main stream.
   std::vector<pmmg_hip_ctx *> lanes;
   bool borrowed_streams = false; // a lane 0: stream / stream2 belong to its parent
   // the split of a group over the node's GPUs (pmmg_comm.hpp): an RCCL
@@ -341,36 +275,6 @@ struct pmmg_hip_ctx {
   // the r05 "slowdown after a large call")
   int group_lanes = 3;
   struct Pool *lane_pool = nullptr; // host threads enqueueing the other lanes' groups
-  int lane_streams = 1; // a group lane's streams: 2 = its own surface stream, 1 = the surface branch on the
-                        // main stream (measurement build: PMMG_HIP_LANE_STREAMS)
-  int bdy_first = 0; // measurement build, PMMG_HIP_BDYFIRST=1: the volume kernel waits for the surface branch
-  int bdy_after = 0; // measurement build, PMMG_HIP_BDYAFTER=1: k_bdy waits for the volume kernel (large calls)
-  int vol_wait_seed = 0; // measurement build, PMMG_HIP_VOLWAIT=1: the volume kernel waits for the surface seeds
-  int lane0 = 1; // lane 0 enqueues on this context's streams (measurement build: PMMG_HIP_LANE0=0 gives it
-                 // streams of its own)
-  // the volume stage split into a walk kernel that writes located records and an interpolation kernel
-  // (r06), measured and not the default: at cfg4 the fused kernel's volume stage 3.30-3.35 ms,
-  // split 3.60-3.66 (arrays) / 3.52 (packed records, one pass), chunked with the interpolation on its own stream
-  // beside the next walk chunk 3.62-3.77 (profiles/r06a-r06c): the walk alone takes 1.91 ms and the
-  // interpolation alone 1.90-1.99, whose sum the fused kernel beats by overlapping them across its waves, and
-  // the located records add 1.9 GB of traffic.  PMMG_HIP_VOLSPLIT: 1 split (every call), 0 fused (default);
-  // -1 split for calls of >= kSmallGroup queries
-  int vol_split = 0;
-  DevBuf locv, locp; // the split stage's located records (LocBuf): vertex ids, coordinates
-  // the split stage in chunks: walk chunk j on the main stream, its interpolation on stream_i after the
-  // chunk's event, so that interpolation j runs beside walk j + 1 (PMMG_HIP_VOLCHUNKS, 1..kMaxVolChunks)
-  static constexpr int kMaxVolChunks = 16;
-  int vol_chunks = 4;
-  hipStream_t stream_i = nullptr;
-  hipEvent_t ev_chunk[2][kMaxVolChunks] = {};
-  hipEvent_t ev_interp = nullptr;
-  int ixcd_run = -1; // measurement build, PMMG_HIP_IXCDRUN: the interpolation kernel's XCD run (-1: xcd_run)
-  int null_sync = 0;   // measurement build, PMMG_HIP_NULLSYNC=1: small reads through the null stream (ctx_d2h)
-  int eager_lanes = 0; // measurement build, PMMG_HIP_EAGERLANES=1: the group lanes created with the context
-  int wave_time = 0;   // measurement build, PMMG_HIP_WAVETIME=1: k_bdy's per-wave wall-clock records, appended
-                       // to the file PMMG_HIP_WAVETIME_OUT at each call's statistics
-  DevBuf wt;
-  size_t wt_n = 0;
   int filter_steps = 64; // step cap of the fp32 filter walk (then the exact fp64 walk continues from where it
                          // stopped: a query the filter misjudges hands over early instead of cycling through a
                          // 4-entry history for up to maxstep steps); test-only PMMG_HIP_FILTER_STEPS=0 sends every
@@ -400,9 +304,8 @@ static void set_err(pmmg_hip_ctx *c, const char *fmt, ...) {
 // user — created at the first such copy — shifted the hardware queues the
 // group lanes' streams were later given (the groups call
 // 25 % slower after any earlier call in the process; tools/groups_probe.py,
-// profiles/r06f).  PMMG_HIP_NULLSYNC=1 (measurement build): the null stream again.
+// profiles/r06f).
 static hipError_t ctx_d2h(pmmg_hip_ctx *c, void *dst, const void *src, size_t n) {
-  if (c->null_sync) return hipMemcpy(dst, src, n, hipMemcpyDeviceToHost);
   hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream);
   return e != hipSuccess ? e : hipStreamSynchronize(c->stream);
 }
@@ -692,8 +595,7 @@ static int env_int(const char *name, int def) { // positive values only
   if (e && atoi(e) > 0) return atoi(e);
   return def;
 }
-// switches whose 0 (or -1) is a setting of its own (env_int reads 0 as unset: up to r06zm the
-// PMMG_HIP_HOSTORDER=0, FUSECONT=0, SRFSOLO=0, LANE0=0, STREAM3=0 and IXCDRUN=0 variants ran the default)
+// switches whose 0 (or -1) is a setting of its own (env_int reads 0 as unset)
 static int env_int_any(const char *name, int def) {
   const char *e = getenv(name);
   if (!e || !*e) return def;
@@ -717,7 +619,7 @@ int pmmg_hip_device_count(void) {
 
 // share != NULL: a group lane that enqueues on share's two streams (its
 // own buffers, events and state; the streams are not destroyed with it)
-static pmmg_hip_ctx *create_ctx(int device, int options, bool srf_prio, pmmg_hip_ctx *share = nullptr) {
+static pmmg_hip_ctx *create_ctx(int device, int options, pmmg_hip_ctx *share = nullptr) {
   int n = pmmg_hip_device_count();
   if (n <= 0 || device < 0 || device >= n) {
     fprintf(stderr, "[parmmg_hip] no HIP device %d (visible: %d)\n", device, n);
@@ -726,12 +628,6 @@ static pmmg_hip_ctx *create_ctx(int device, int options, bool srf_prio, pmmg_hip
   pmmg_hip_ctx *c = new pmmg_hip_ctx();
   c->device = device;
   c->options = options;
-#ifdef PMMG_HIP_MEASURE
-  if (const char *e = getenv("PMMG_HIP_SRFPRIO"))
-    if (*e == '1') c->srf_prio = srf_prio;
-#else
-  (void)srf_prio;
-#endif
   if (share) {
     c->stream = share->stream;
     c->stream2 = share->stream2;
@@ -744,17 +640,7 @@ static pmmg_hip_ctx *create_ctx(int device, int options, bool srf_prio, pmmg_hip
     delete c;
     return nullptr;
   }
-  {
-    // measurement build, PMMG_HIP_EVFLAGS: 1 = the call's events without the system-scope fence, 2 = with a
-    // device-scope release; the order decision's EV_FRAME (read by the host) and EV_END keep the default
-    int evf = 0;
-#ifdef PMMG_HIP_MEASURE
-    evf = env_int("PMMG_HIP_EVFLAGS", 0);
-#endif
-    const unsigned fl = evf == 1 ? hipEventDisableSystemFence : (evf == 2 ? hipEventReleaseToDevice : 0u);
-    for (int i = 0; i < EV_COUNT; i++)
-      (void)hipEventCreateWithFlags(&c->ev[i], (i == EV_FRAME || i == EV_END) ? hipEventDefault : fl);
-  }
+  for (int i = 0; i < EV_COUNT; i++) (void)hipEventCreateWithFlags(&c->ev[i], hipEventDefault);
   // documented options, each clamped to its valid range
   c->tpc = std::min(4096, env_int("PMMG_HIP_TPC", c->tpc));
   c->srf_mult = std::min(4096, env_int("PMMG_HIP_SRFMULT", c->srf_mult));
@@ -767,58 +653,14 @@ static pmmg_hip_ctx *create_ctx(int device, int options, bool srf_prio, pmmg_hip
   c->fanmax = env_int("PMMG_HIP_FANMAX", c->fanmax);
   c->srf_g = std::min(1024, env_int("PMMG_HIP_SRFG", 0));
   c->pack_passes = std::max(0, std::min(2, env_int("PMMG_HIP_PACKPASS", c->pack_passes))); // packed: gather passes
-  if (const char *e = getenv("PMMG_HIP_VOLSPLIT"))
-    if (*e == '0' || *e == '1') c->vol_split = *e - '0';
-  c->vol_chunks = std::max(1, std::min((int)pmmg_hip_ctx::kMaxVolChunks, env_int("PMMG_HIP_VOLCHUNKS", c->vol_chunks)));
   c->bg.fanmax = c->fanmax; // every kernel's Bg copy carries it
   c->filter_steps = c->filter_steps < c->maxstep ? c->filter_steps : c->maxstep;
   if (const char *e = getenv("PMMG_HIP_FILTER_STEPS"))
     if (*e && atoi(e) >= 0) c->filter_steps = atoi(e);
-#ifdef PMMG_HIP_MEASURE
-  // A/B switches of the measurement build (libpmmg_hip_measure.so, tools/)
-  c->seed_lanes = std::min(4, env_int("PMMG_HIP_SEEDLANES", c->seed_lanes));
-  c->seed_v0 = (env_int("PMMG_HIP_SEEDV0", 0) == 1 ? 1 : 0) | (env_int("PMMG_HIP_SEEDNOATOM", 0) == 1 ? 2 : 0);
-  c->bbox_stride = env_int("PMMG_HIP_BBOX", c->bbox_stride);
-  c->hist_stride = env_int("PMMG_HIP_HIST", c->hist_stride);
-  c->bdy_dyn = (env_int("PMMG_HIP_BDYDYN", 2) == 1 ? 1 : 0) | (env_int("PMMG_HIP_BDYNOINTERP", 0) == 1 ? 2 : 0);
-  c->bdy_bpx = env_int("PMMG_HIP_BDYBPX", c->bdy_bpx);
-  c->bdy_wave = env_int("PMMG_HIP_BDYWAVE", c->bdy_wave);
-  c->host_order = env_int_any("PMMG_HIP_HOSTORDER", c->host_order);
-  c->fuse_cont = env_int_any("PMMG_HIP_FUSECONT", c->fuse_cont);
-  c->quant_side = env_int("PMMG_HIP_QUANTSIDE", c->quant_side);
-  c->bin_qs = env_int("PMMG_HIP_BINQS", 2) == 1;
-  c->brick = env_int("PMMG_HIP_BRICK", 0);
-  c->srf_solo = env_int_any("PMMG_HIP_SRFSOLO", -1);
-  c->set_order = env_int("PMMG_HIP_SETORDER", 0);
-  if (const char *e = getenv("PMMG_HIP_XCDRUN"))
-    if (*e && atoi(e) >= 0) c->xcd_run = atoi(e);
-  c->pad = env_int("PMMG_HIP_PAD", 0);
-  c->ixcd_run = env_int_any("PMMG_HIP_IXCDRUN", -1);
-  c->null_sync = env_int("PMMG_HIP_NULLSYNC", 0);
-  c->eager_lanes = env_int("PMMG_HIP_EAGERLANES", 0);
-  c->wave_time = env_int("PMMG_HIP_WAVETIME", 0);
-  c->lane_streams = std::max(1, std::min(3, env_int("PMMG_HIP_LANE_STREAMS", c->lane_streams)));
-  c->lane0 = env_int_any("PMMG_HIP_LANE0", 1) ? 1 : 0;
-  c->bdy_first = env_int("PMMG_HIP_BDYFIRST", 0);
-  c->bdy_after = env_int("PMMG_HIP_BDYAFTER", 0);
-  c->vol_wait_seed = env_int("PMMG_HIP_VOLWAIT", 0);
-  c->no_fb = env_int("PMMG_HIP_NOFB", 0);
-  c->stream3_mode = env_int_any("PMMG_HIP_STREAM3", c->stream3_mode);
-  if (c->stream3_mode == 2 && hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking) != hipSuccess)
-    c->stream3 = nullptr; // the exhaustive kernels not launched (a launch's price; wrong results
-                                           // wherever a query needs them)
-#endif
   return c;
 }
 
-static pmmg_hip_ctx *group_lane(pmmg_hip_ctx *c, int j);
-
-pmmg_hip_ctx *pmmg_hip_create(int device, int options) {
-  pmmg_hip_ctx *c = create_ctx(device, options, true);
-  if (c && c->eager_lanes)
-    for (int j = 0; j < c->group_lanes; j++) (void)group_lane(c, j);
-  return c;
-}
+pmmg_hip_ctx *pmmg_hip_create(int device, int options) { return create_ctx(device, options); }
 
 void pmmg_hip_destroy(pmmg_hip_ctx *c) {
   if (!c) return;
@@ -828,26 +670,15 @@ void pmmg_hip_destroy(pmmg_hip_ctx *c) {
   (void)snap_join(c);
   (void)hipStreamSynchronize(c->stream);
   (void)hipStreamSynchronize(c->stream2);
-  if (c->stream2_hi) (void)hipStreamSynchronize(c->stream2_hi);
   if (c->stream3) (void)hipStreamSynchronize(c->stream3);
   if (c->stream_f) (void)hipStreamSynchronize(c->stream_f);
   if (c->cstream) (void)hipStreamSynchronize(c->cstream);
-  if (c->stream_i) {
-    (void)hipStreamSynchronize(c->stream_i);
-    (void)hipStreamDestroy(c->stream_i);
-  }
-  for (auto &row : c->ev_chunk)
-    for (hipEvent_t &e : row)
-      if (e) (void)hipEventDestroy(e);
-  if (c->ev_interp) (void)hipEventDestroy(c->ev_interp);
   DevBuf *bufs[] = {&c->o_xyz, &c->o_tetv, &c->o_adja, &c->o_triv, &c->o_adjt, &c->o_met, &c->o_rec, &c->frame,
                     &c->stats, &c->grid, &c->sgrid, &c->order_v, &c->cohd,
-                    &c->order_b, &c->cont, &c->xq, &c->qs, &c->axh, &c->bkeys, &c->bkeys2, &c->bvals, &c->bvals2, &c->rs_hist, &c->rs_csum, &c->oflag, &c->cls_cnt, &c->qmin, &c->fb_vol, &c->fb_bdy,
+                    &c->order_b, &c->xq, &c->axh, &c->bkeys, &c->bkeys2, &c->bvals, &c->bvals2, &c->rs_hist, &c->rs_csum, &c->oflag, &c->cls_cnt, &c->qmin, &c->fb_vol, &c->fb_bdy,
                     &c->best, &c->nac, &c->cres, &c->bbest, &c->bnac, &c->bcres, &c->fbp_vol, &c->fbp_bdy, &c->fbg_vol_c,
                     &c->fbg_vol_u, &c->fbg_vol_i, &c->fbg_bdy_c, &c->fbg_bdy_u, &c->fbg_bdy_i, &c->h_xyz,
-                    &c->h_cls, &c->h_met, &c->h_elem, &c->h_hit, &c->brk_k, &c->brk_k2, &c->brk_v, &c->brk_v2,
-                    &c->brk_vinv, &c->brk_tinv, &c->brk_xq, &c->brk_xyz, &c->brk_sol, &c->brk_rec, &c->brk_tmp,
-                    &c->locv, &c->locp, &c->wt, &c->map_own, &c->map_need, &c->start_tab};
+                    &c->h_cls, &c->h_met, &c->h_elem, &c->h_hit, &c->map_own, &c->map_need, &c->start_tab};
   for (DevBuf *b : bufs) release(*b);
   for (auto &b : c->o_f) release(b);
   for (auto &b : c->h_f) release(b);
@@ -875,7 +706,6 @@ void pmmg_hip_destroy(pmmg_hip_ctx *c) {
     if (c->stream2 && c->stream2 != c->stream) (void)hipStreamDestroy(c->stream2);
     if (c->stream) (void)hipStreamDestroy(c->stream);
   }
-  if (c->stream2_hi) (void)hipStreamDestroy(c->stream2_hi);
   if (c->stream3) (void)hipStreamDestroy(c->stream3);
   if (c->stream_f) (void)hipStreamDestroy(c->stream_f);
   if (c->flag_host) (void)hipHostFree(c->flag_host);
@@ -1420,56 +1250,6 @@ static void launch_bdy_fallbacks(pmmg_hip_ctx *c, hipStream_t s, const Slots &S,
                         (const int *)c->bnac.p, (FbPart *)c->fbp_bdy.p, (int *)c->bcres.p, S, elem_out, hit_out);
 }
 
-#ifdef PMMG_HIP_MEASURE
-// PMMG_HIP_BRICK=b: the background renumbered by bricks of b^3 seed cells
-// (measurement only: pmmg_brick.hpp); the results go nowhere
-static int brick_renumber(pmmg_hip_ctx *c, hipStream_t s, const Bg &bg, const Slots &S, const Frame *fr, int g) {
-  int lb = 0;
-  while ((2 << lb) <= c->brick) lb++;
-  const size_t nmax = (size_t)(bg.np > bg.ne ? bg.np : bg.ne);
-  size_t nsol = 0;
-  for (int j = 0; j < S.n; j++) nsol += (size_t)S.s[j].code;
-  if (!ensure(c, c->brk_k, 4 * nmax) || !ensure(c, c->brk_k2, 4 * nmax) || !ensure(c, c->brk_v, 4 * nmax) ||
-      !ensure(c, c->brk_v2, 4 * nmax) || !ensure(c, c->brk_vinv, 4 * (size_t)bg.np) ||
-      !ensure(c, c->brk_tinv, 4 * (size_t)bg.ne) || !ensure(c, c->brk_xq, 4 * kXqStride * (size_t)bg.np) ||
-      !ensure(c, c->brk_xyz, 24 * (size_t)bg.np) || !ensure(c, c->brk_sol, 8 * nsol * (size_t)bg.np + 8) ||
-      !ensure(c, c->brk_rec, 32 * (size_t)bg.ne))
-    return 0;
-  unsigned *k1 = (unsigned *)c->brk_k.p, *k2 = (unsigned *)c->brk_k2.p;
-  int *v1 = (int *)c->brk_v.p, *v2 = (int *)c->brk_v2.p;
-  int *vinv = (int *)c->brk_vinv.p, *tinv = (int *)c->brk_tinv.p;
-  const int kbits = 3 * (10 - lb);
-  size_t tmp = 0;
-  HIPCK(c, rocprim::radix_sort_pairs(nullptr, tmp, (const unsigned *)k1, k2, (const int *)v1, v2, nmax, 0, kbits, s));
-  if (!ensure(c, c->brk_tmp, tmp)) return 0;
-  // vertices: keys, sort, inverse, rows
-  hipLaunchKernelGGL(k_brick_vkeys, dim3(blocks_for(bg.np, 4096)), dim3(kBlock), 0, s, bg, fr, g, lb, k1, v1);
-  HIPCK(c, rocprim::radix_sort_pairs(c->brk_tmp.p, tmp, (const unsigned *)k1, k2, (const int *)v1, v2, (size_t)bg.np, 0,
-                                     kbits, s));
-  hipLaunchKernelGGL(k_brick_inv, dim3(blocks_for(bg.np, 4096)), dim3(kBlock), 0, s, (const int *)v2,
-                     (long long)bg.np, vinv);
-  hipLaunchKernelGGL(k_brick_vrows, dim3(blocks_for(bg.np, 4096)), dim3(kBlock), 0, s, bg, (const int *)v2,
-                     (int *)c->brk_xq.p, (double *)c->brk_xyz.p);
-  size_t off = 0;
-  for (int j = 0; j < S.n; j++) {
-    hipLaunchKernelGGL(k_brick_srows, dim3(blocks_for((long long)bg.np * S.s[j].code, 4096)), dim3(kBlock), 0, s,
-                       S.s[j].in, S.s[j].istride, S.s[j].code, (const int *)v2, (long long)bg.np,
-                       (double *)c->brk_sol.p + off * (size_t)bg.np);
-    off += (size_t)S.s[j].code;
-  }
-  // tetra: keys, sort, inverse, records (vertex ids and adjacencies renumbered)
-  hipLaunchKernelGGL(k_brick_tkeys, dim3(blocks_for(bg.ne, 4096)), dim3(kBlock), 0, s, bg, fr, g, lb, k1, v1);
-  HIPCK(c, rocprim::radix_sort_pairs(c->brk_tmp.p, tmp, (const unsigned *)k1, k2, (const int *)v1, v2, (size_t)bg.ne, 0,
-                                     kbits, s));
-  hipLaunchKernelGGL(k_brick_inv, dim3(blocks_for(bg.ne, 4096)), dim3(kBlock), 0, s, (const int *)v2, (long long)bg.ne,
-                     tinv);
-  hipLaunchKernelGGL(k_brick_trec, dim3(blocks_for(bg.ne, 4096)), dim3(kBlock), 0, s, bg, (const int *)v2,
-                     (const int *)vinv, (const int *)tinv, (int4 *)c->brk_rec.p);
-  HIPCK(c, hipGetLastError());
-  return 1;
-}
-#endif
-
 // The background's start tables (pmmg_prep.hpp: point map), built on the
 // main stream when the background has none yet: start_tet[np], start_tri[np].
 static int start_tables(pmmg_hip_ctx *c) {
@@ -1488,35 +1268,50 @@ static int start_tables(pmmg_hip_ctx *c) {
   return 1;
 }
 
-// The pipeline of one call on device pointers.  It enqueues its kernels on
-// the context's two streams and reads nothing back: in auto order mode both
-// the Morton binning and the input-order compaction are enqueued, each gated
-// on the coherence test's flag on the device (r04), and every fallback kernel
-// reads its list's count on the device.
-static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const uint8_t *pclass, double *met_out,
-                      double *const *fields_out, int *elem_out, int8_t *hit_out, double *rec_out = nullptr,
-                      const int *map_src = nullptr) {
-  Bg bg = c->bg;
-  hipStream_t s = c->stream, sb = c->stream2;
-  // Measurement build (PMMG_HIP_SRFPRIO=1): a large call runs its second
-  // stream (query order, then the surface branch) at the highest priority, so
-  // k_bdy's blocks are dispatched ahead of the volume kernel's instead of
-  // trailing it (r04o trace: the surface branch ended 0.17 ms after the
-  // volume kernel; cfg4 -0.06 ms, r04zh).  Not in the product: once a
-  // high-priority stream has existed in the process — even destroyed — the
-  // groups call's lanes run at 0.22-0.33 instead of 0.095 ms per cfg2-size
-  // group (r04x, r04zg).  The second stream always waits for the main
-  // stream's first event, so a call may use either.
-  if (c->srf_prio && np_new >= kSmallGroup) {
-    if (!c->stream2_hi) {
-      int prio_lo = 0, prio_hi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-      if (hipStreamCreateWithPriority(&c->stream2_hi, hipStreamNonBlocking, prio_hi) != hipSuccess)
-        c->stream2_hi = nullptr;
-    }
-    if (c->stream2_hi) sb = c->stream2_hi;
-  }
-  Slots S{};
+// ---------------------------------------------------------------- one call on device pointers
+//
+// run_device enqueues one call's kernels on the context's streams, stage by
+// stage (the functions below, in the order they run); every fallback kernel
+// reads its list's count on the device.  Only a large call in auto order mode
+// reads something back: the coherence test's decision, once (run_device).
+
+// Measured settings, runtime arguments of the kernels that take them
+constexpr int kSeedLanes = 4;    // sampled tetra per seed run of 4 records (1..4)
+constexpr int kBboxStride = 64;  // the frame's bbox samples np / 64 vertices (r03o: 64 instead of 16 and
+constexpr int kHistStride = 256; // 256 instead of 64 for the axis histograms: preparation -0.15 ms at cfg4, same walks)
+constexpr int kBdyBpx = 512;     // k_bdy blocks per XCD at most, in blocks of kBlock threads
+constexpr int kXcdRun = 64;      // k_vol's blocks dealt to the XCDs in runs of 64 (4096 queries) instead of contiguous
+                                 // eighths: r04c at cfg4, volume kernel 3.80 -> 3.50 ms, Mmg-like numbering 5.83 -> 4.14 ms
+
+// One call's arguments and what its stages share
+struct Call {
+  pmmg_hip_ctx *c;
+  int np_new;
+  const double *xyz_new;
+  const uint8_t *pclass;
+  int *elem_out;
+  int8_t *hit_out;
+  Bg bg;                 // the context's background with the call's fixed-point copy (xq)
+  hipStream_t s, sb, sc; // main stream, surface stream, the Morton binning's stream (sb when it has none of its own)
+  Slots S;
+  VolFn vol_fn;
+  MapArgs ma; // a call with a point map (else nulls)
+  int *need;  // its counts of queries the map gives no start {volume, surface}, which gate the seed grids (else null)
+  int force;  // the query order: 1 Morton, 0 input; -1 while a large auto-order call's decision is on its way
+  int g, gs;  // cells per axis of the volume / surface seed grid
+  long long ng, nsg, ncls; // their cells; blocks of the surface list's compaction
+  Frame *fr;
+  DevStats *st;
+  unsigned long long *grid, *sgrid;
+  int *order_v, *order_b;
+  const int *flag; // the order decision on the device {sorted, bits per axis}
+};
+
+// ---- slots and layout: the arguments checked, the solutions' slots, the volume kernel for their layout, the
+// point map's start tables
+static int call_slots(Call &k, double *met_out, double *const *fields_out, double *rec_out, const int *map_src) {
+  pmmg_hip_ctx *c = k.c;
+  Slots &S = k.S;
   S.n = 0;
   S.has_met = c->met_size ? 1 : 0;
   if (rec_out && !c->rec) {
@@ -1551,43 +1346,37 @@ static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const 
     }
     S.rec_out = rec_out;
   }
-  const VolPick vpick = pick_layout(S, c->pack_passes, map_src != nullptr);
-  if (!vpick.fn) {
+  k.vol_fn = pick_layout(S, c->pack_passes, map_src != nullptr);
+  if (!k.vol_fn) {
     set_err(c, "locate_interp: no packed-record kernel for this slot layout");
     return 0;
   }
-  const bool vsplit = S.n > 0 && vpick.ifn && (c->vol_split < 0 ? np_new >= kSmallGroup : c->vol_split == 1);
-  LocBuf lb{nullptr, nullptr, nullptr};
-  if (vsplit) {
-    if (!ensure(c, c->locv, 16 * (size_t)np_new) || !ensure(c, c->locp, 32 * (size_t)np_new)) return 0;
-    lb = LocBuf{(nti4 *)c->locv.p, (ntd2 *)c->locp.p, (ntd2 *)c->locp.p + np_new};
-    if (!c->stream_i) HIPCK(c, hipStreamCreateWithFlags(&c->stream_i, hipStreamNonBlocking));
-    for (auto &row : c->ev_chunk)
-      for (hipEvent_t &e : row)
-        if (!e) HIPCK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (!c->ev_interp) HIPCK(c, hipEventCreateWithFlags(&c->ev_interp, hipEventDisableTiming));
-  }
-  const VolFn vol_fn = vsplit ? (map_src ? kVolWalkMap : kVolWalk) : vpick.fn;
   // a call with a point map: the background's start tables (built now if it has none), and the counts of
   // queries the map gives no start, which gate the seed grids on the device
-  MapArgs ma{nullptr, nullptr, nullptr};
-  int *need = nullptr;
+  k.ma = MapArgs{nullptr, nullptr, nullptr};
+  k.need = nullptr;
   if (map_src) {
     if (!start_tables(c) || !ensure(c, c->map_need, 2 * sizeof(int))) return 0;
-    need = (int *)c->map_need.p;
-    ma = MapArgs{map_src, (const int *)c->start_tab.p, (const int *)c->start_tab.p + bg.np};
+    k.need = (int *)c->map_need.p;
+    k.ma = MapArgs{map_src, (const int *)c->start_tab.p, (const int *)c->start_tab.p + k.bg.np};
   }
-  const int g = grid_dim(bg.ne, c->tpc, 1024);
-  const int gs = bg.nt <= 0 ? 1 : (c->srf_g > 0 ? c->srf_g : grid_dim((long long)bg.nt * c->srf_mult, 2, 1024));
-  const int gb = 1 << kBinBitsAxis;
-  const size_t nq = (size_t)np_new;
-  const long long ng = (long long)g * g * g, nsg = bg.nt > 0 ? (long long)gs * gs * gs : 0;
-  const long long ncls = (long long)(nq / kScanChunk + 1);
+  return 1;
+}
+
+// ---- scratch: the grids' sizes, the work buffers, the query order known at entry
+static int call_scratch(Call &k) {
+  pmmg_hip_ctx *c = k.c;
+  Bg &bg = k.bg;
+  k.g = grid_dim(bg.ne, c->tpc, 1024);
+  k.gs = bg.nt <= 0 ? 1 : (c->srf_g > 0 ? c->srf_g : grid_dim((long long)bg.nt * c->srf_mult, 2, 1024));
+  const size_t nq = (size_t)k.np_new;
+  k.ng = (long long)k.g * k.g * k.g;
+  k.nsg = bg.nt > 0 ? (long long)k.gs * k.gs * k.gs : 0;
+  k.ncls = (long long)(nq / kScanChunk + 1);
   if (!ensure(c, c->frame, sizeof(Frame)) || !ensure(c, c->stats, sizeof(DevStats) + kStatParts * sizeof(StatPart)) ||
-      !ensure(c, c->grid, 8 * (size_t)ng) || !ensure(c, c->sgrid, 8 * (size_t)nsg) || !ensure(c, c->order_v, 4 * nq) ||
-      !ensure(c, c->order_b, 4 * nq) || !ensure(c, c->cont, sizeof(ContEntry) * nq) ||
-      !ensure(c, c->bkeys, 4 * nq) || !ensure(c, c->bkeys2, 4 * nq) || !ensure(c, c->bvals, 4 * nq) ||
-      !ensure(c, c->qs, 24 * nq) || !ensure(c, c->cls_cnt, 4 * (size_t)ncls) || 
+      !ensure(c, c->grid, 8 * (size_t)k.ng) || !ensure(c, c->sgrid, 8 * (size_t)k.nsg) ||
+      !ensure(c, c->order_v, 4 * nq) || !ensure(c, c->order_b, 4 * nq) || !ensure(c, c->bkeys, 4 * nq) ||
+      !ensure(c, c->bkeys2, 4 * nq) || !ensure(c, c->bvals, 4 * nq) || !ensure(c, c->cls_cnt, 4 * (size_t)k.ncls) ||
       !ensure(c, c->fb_vol, 4 * nq) || !ensure(c, c->fb_bdy, 4 * nq) || !ensure(c, c->best, 4 * nq) ||
       !ensure(c, c->nac, 4 * nq) || !ensure(c, c->cres, 4 * nq) || !ensure(c, c->bbest, 4 * nq) ||
       !ensure(c, c->bnac, 4 * nq) || !ensure(c, c->bcres, 4 * nq) ||
@@ -1602,21 +1391,24 @@ static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const 
       !ensure(c, c->axh, sizeof(int) * 3 * kMapBins * (size_t)kHistBlocks))
     return 0;
   bg.xq = (const int *)c->xq.p;
-  Frame *fr = (Frame *)c->frame.p;
-  DevStats *st = (DevStats *)c->stats.p;
-  unsigned long long *grid = (unsigned long long *)c->grid.p;
-  unsigned long long *sgrid = (unsigned long long *)c->sgrid.p;
-  int *order_v = (int *)c->order_v.p, *order_b = (int *)c->order_b.p;
-  int force = (c->options & PMMG_HIP_OPT_SORT) ? 1 : (c->options & PMMG_HIP_OPT_NOSORT) ? 0 : -1;
-  if (force < 0 && np_new < kSmallGroup) force = 0;
+  k.fr = (Frame *)c->frame.p;
+  k.st = (DevStats *)c->stats.p;
+  k.grid = (unsigned long long *)c->grid.p;
+  k.sgrid = (unsigned long long *)c->sgrid.p;
+  k.order_v = (int *)c->order_v.p;
+  k.order_b = (int *)c->order_b.p;
+  k.flag = (const int *)c->oflag.p;
+  // Forced orders enqueue only theirs; a small group (below kSmallGroup queries: its background and solutions
+  // stay in the Infinity Cache, where a numbering's locality matters little) takes the input order untested.
+  k.force = (c->options & PMMG_HIP_OPT_SORT) ? 1 : (c->options & PMMG_HIP_OPT_NOSORT) ? 0 : -1;
+  if (k.force < 0 && k.np_new < kSmallGroup) k.force = 0;
   // r06: a large auto-order call reads the decision back once k_bbox is done (the host waits while the device
   // runs the fixed-point copy and the seed grid, ~0.4 ms at cfg4) and enqueues only the chosen order's
   // kernels.  With both orders enqueued and gated on the device, the input order's volume kernel waited for
   // the ~19 gated binning launches (each dispatched only when the preparation kernels left a slot free: they
   // ended 20-55 us after the seed grid, profiles/r06i, r06k), or, below 2^23 queries, the other order's
   // volume launch returned at once in 40-64k one-wave blocks (~35-55 us of dispatch on the main stream).
-  const bool host_order = force < 0 && c->host_order;
-  if (host_order && !c->flag_host) {
+  if (k.force < 0 && !c->flag_host) {
     void *p = nullptr;
     HIPCK(c, hipHostMalloc(&p, 64, hipHostMallocCoherent | hipHostMallocMapped));
     c->flag_host = (int *)p;
@@ -1624,261 +1416,260 @@ static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const 
     HIPCK(c, hipHostGetDevicePointer(&d, p, 0));
     c->flag_host_dev = (int *)d;
   }
-  if (host_order) c->flag_host[0] = -1;
+  if (k.force < 0) c->flag_host[0] = -1;
+  return 1;
+}
 
-  // ---- frame (main stream).  The call's events ride on its kernels' dispatches where a kernel is at hand
-  // (hipExtLaunchKernelGGL start / stop events): a separate marker between two kernels of a stream cost the
-  // device ~4 us, an event on the dispatch ~1.7 (tools/calib/ext_event.hip, profiles/r06zj)
+// ---- frame and seeds (main stream): reset, the map's counts, the frame with the coherence test, the fixed-point
+// copy and the axis maps, the volume seed grid; the other streams are told what to wait for in between.
+// The call's events ride on its kernels' dispatches where a kernel is at hand (hipExtLaunchKernelGGL start /
+// stop events): a separate marker between two kernels of a stream cost the device ~4 us, an event on the
+// dispatch ~1.7 (tools/calib/ext_event.hip, profiles/r06zj)
+static int launch_frame_seeds(Call &k) {
+  pmmg_hip_ctx *c = k.c;
+  const Bg &bg = k.bg;
+  const int force = k.force;
+  hipStream_t s = k.s;
   // seed grids: cleared here unless the previous call left them clean (a
   // large grid is refilled at the end of the call that used it, beside the
   // other stream's tail: r05, cfg4 k_reset 32 us -> the stats only)
-  const long long ng_clr = (c->grid.p == c->grid_clean_p && ng <= c->grid_clean_n) ? 0 : ng;
-  const long long nsg_clr = (c->sgrid.p == c->sgrid_clean_p && nsg <= c->sgrid_clean_n) ? 0 : nsg;
+  const long long ng_clr = (c->grid.p == c->grid_clean_p && k.ng <= c->grid_clean_n) ? 0 : k.ng;
+  const long long nsg_clr = (c->sgrid.p == c->sgrid_clean_p && k.nsg <= c->sgrid_clean_n) ? 0 : k.nsg;
   c->grid_clean_n = c->sgrid_clean_n = 0; // dirty until this call's refill is enqueued
   // the input order's surface list needs only the zeroed counters (and the coherence flag), not the frame
-  // (r06: EV_RESET is waited for only in a forced order, EV_VOL0 / EV_VOL only when a kernel separates them
-  // from EV_PREP / EV_WALK)
+  // (r06: EV_RESET is waited for only in a forced order, EV_VOL0 only when a kernel separates it from EV_PREP)
   hipExtLaunchKernelGGL(k_reset, dim3(blocks_for(ng_clr > nsg_clr ? ng_clr : nsg_clr, 2048)), dim3(kBlock), 0, s,
-                        c->ev[EV_START], force >= 0 ? c->ev[EV_RESET] : nullptr, 0, fr, st, grid, ng_clr, sgrid,
+                        c->ev[EV_START], force >= 0 ? c->ev[EV_RESET] : nullptr, 0, k.fr, k.st, k.grid, ng_clr, k.sgrid,
                         nsg_clr, (int *)c->oflag.p, force, c->bin_bits);
-  if (map_src) {
-    HIPCK(c, hipMemsetAsync(need, 0, 2 * sizeof(int), s));
-    hipLaunchKernelGGL(k_map_count, dim3(blocks_for(np_new, 2048)), dim3(kBlock), 0, s, pclass, (long long)np_new, ma,
-                       bg.np, bg.ne, bg.nt, need);
+  if (k.need) {
+    HIPCK(c, hipMemsetAsync(k.need, 0, 2 * sizeof(int), s));
+    hipLaunchKernelGGL(k_map_count, dim3(blocks_for(k.np_new, 2048)), dim3(kBlock), 0, s, k.pclass,
+                       (long long)k.np_new, k.ma, bg.np, bg.ne, bg.nt, k.need);
   }
   // bbox (its last block finalises the frame), the seed grid's axis maps
   // (auto order: the queries' coherence test rides along, its flag read by the order and volume kernels)
   // the second stream needs the frame only (lo, inv_bin, inv_srf), not the
   // axis maps (r04: EV_FRAME moved here from after k_axis_map)
-  hipExtLaunchKernelGGL(k_bbox, dim3(std::max(force < 0 ? kCohBlocks : 1, blocks_for(bg.np / c->bbox_stride + 1, 256))),
-                        dim3(kBlock), 0, s, nullptr, c->ev[EV_FRAME], 0, (const double *)bg.xyz, bg.np, fr,
-                        c->bbox_stride, g, gs, gb, xyz_new, np_new, force < 0 ? (int *)c->oflag.p : nullptr,
-                        (double *)c->cohd.p, host_order ? c->flag_host_dev : nullptr);
-  // fixed-point vertex copy + the axis histograms (first kHistBlocks blocks), then the axis maps.
-  // quant_side (r06, large calls): the histograms alone on the main stream, the copy on a stream of its own
-  // beside the seed grid, which then takes its centroids from the fp64 rows; the volume kernel waits for both
-  const bool quant_side = c->quant_side && np_new >= kSmallGroup;
-  if (quant_side) {
-    if (!c->stream_f) HIPCK(c, hipStreamCreateWithFlags(&c->stream_f, hipStreamNonBlocking));
-    HIPCK(c, hipStreamWaitEvent(c->stream_f, c->ev[EV_FRAME], 0));
-    hipLaunchKernelGGL(k_quantize, dim3(blocks_for(3LL * bg.np, 8192)), dim3(kBlock), 0, c->stream_f, bg.xyz,
-                       (long long)bg.np, (const Frame *)fr, (int *)c->xq.p, c->hist_stride, (int *)nullptr);
-    HIPCK(c, hipEventRecord(c->ev[EV_QUANT], c->stream_f));
-    hipLaunchKernelGGL(k_axis_hist, dim3(kHistBlocks), dim3(kBlock), 0, s, bg.xyz, (long long)bg.np,
-                       (const Frame *)fr, c->hist_stride, (int *)c->axh.p);
-  } else {
-    hipLaunchKernelGGL(k_quantize, dim3(std::max(kHistBlocks, blocks_for(3LL * bg.np, 8192))), dim3(kBlock), 0, s,
-                       bg.xyz, (long long)bg.np, (const Frame *)fr, (int *)c->xq.p, c->hist_stride, (int *)c->axh.p);
-  }
-  hipLaunchKernelGGL(k_axis_map, dim3(3), dim3(kBlock), 0, s, (const int *)c->axh.p, fr, g);
+  hipExtLaunchKernelGGL(k_bbox, dim3(std::max(force < 0 ? kCohBlocks : 1, blocks_for(bg.np / kBboxStride + 1, 256))),
+                        dim3(kBlock), 0, s, nullptr, c->ev[EV_FRAME], 0, (const double *)bg.xyz, bg.np, k.fr,
+                        kBboxStride, k.g, k.gs, 1 << kBinBitsAxis, k.xyz_new, k.np_new,
+                        force < 0 ? (int *)c->oflag.p : nullptr, (double *)c->cohd.p,
+                        force < 0 ? c->flag_host_dev : nullptr);
+  // fixed-point vertex copy + the axis histograms (first kHistBlocks blocks), then the axis maps
+  hipLaunchKernelGGL(k_quantize, dim3(std::max(kHistBlocks, blocks_for(3LL * bg.np, 8192))), dim3(kBlock), 0, s,
+                     bg.xyz, (long long)bg.np, (const Frame *)k.fr, (int *)c->xq.p, kHistStride, (int *)c->axh.p);
+  hipLaunchKernelGGL(k_axis_map, dim3(3), dim3(kBlock), 0, s, (const int *)c->axh.p, k.fr, k.g);
   HIPCK(c, hipGetLastError());
 
-  // ---- query order (second stream, concurrent with the seed grid), after
+  // the query order's stream (second stream, concurrent with the seed grid), after
   // the frame.  (r04: the axis maps moved here beside the fixed-point copy
   // cost 10 groups 0.11 -> 0.25 ms per group and the 8-way rank +0.02 ms for
   // -0.0 at cfg4, `profiles/r04s`: not kept)
-  HIPCK(c, hipStreamWaitEvent(sb, c->ev[force < 0 ? EV_FRAME : EV_RESET], 0)); // (the order flag)
+  HIPCK(c, hipStreamWaitEvent(k.sb, c->ev[force < 0 ? EV_FRAME : EV_RESET], 0)); // (the order flag)
   // (EV_SB0: the start of the surface list's first kernel when there is one, launch_cls)
-  if (force == 1 || bg.nt <= 0) HIPCK(c, hipEventRecord(c->ev[EV_SB0], sb));
-  // the Morton binning on a third stream (r05, `profiles/r05m`: on the second stream its ~19 launches, each
-  // returning at once when the coherence test picks input order, held the 8-way rank's volume kernel 86 us
-  // behind the seed grid)
-  hipStream_t sc = sb;
+  if (force == 1 || bg.nt <= 0) HIPCK(c, hipEventRecord(c->ev[EV_SB0], k.sb));
+  // the Morton binning on a third stream (r05, `profiles/r05m`: on the second stream its ~19 launches held the
+  // 8-way rank's volume kernel 86 us behind the seed grid)
+  k.sc = k.sb;
   if (force != 0) {
-    if (c->stream3_mode == 1 && !c->stream3 &&
-        hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking) != hipSuccess)
+    if (!c->stream3 && hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking) != hipSuccess)
       c->stream3 = nullptr;
-    if (c->stream3) sc = c->stream3;
-    HIPCK(c, hipStreamWaitEvent(sc, c->ev[EV_FRAME], 0)); // (the frame and the order flag)
-  }
-  // auto mode with the binning on its own stream (split): the input order's lists (EV_ORDER, second stream)
-  // and the Morton order's (EV_ORDER2, third stream) are waited for separately, each by the launch of the
-  // volume / surface kernel for its order (the other launch returns at once): a call in input order no longer
-  // waits for the ~19 binning launches, which return at once but take ~130 us in a row (r05n, 8-way rank).
-  // Below 2^23 queries: a larger call's seed grid outlasts the binning chain anyway (cfg4's preparation
-  // 0.41 ms) and keeps one volume launch per call.
-  bool split = force < 0 && sc != sb && np_new < (1 << 23);
-  HIPCK(c, hipGetLastError());
-
-  // ---- seed grid (main stream): volume seeds
-  {
-    const long long nsamp = ng < bg.ne ? ng : bg.ne;
-    // kSeedBatch samples per thread in flight together (r05m: one per thread, the 8-way rank's 1.65M samples
-    // took 107 us — the grid's latency in rounds of waves — where cfg4's 12.6M take 262 us)
-    hipExtLaunchKernelGGL(k_seed_vol, dim3((blocks_for((nsamp + kSeedBatch - 1) / kSeedBatch, 8192) + 7) & ~7),
-                          dim3(kBlock), 0, s, nullptr, quant_side ? nullptr : c->ev[EV_PREP], 0, bg, fr, grid, g,
-                          nsamp, c->seed_lanes, c->seed_v0, quant_side ? bg.xyz : (const double *)nullptr,
-                          (const int *)need);
-    if (quant_side) { // (the walk reads the fixed-point copy)
-      HIPCK(c, hipStreamWaitEvent(s, c->ev[EV_QUANT], 0));
-      HIPCK(c, hipEventRecord(c->ev[EV_PREP], s));
-    }
+    if (c->stream3) k.sc = c->stream3;
+    HIPCK(c, hipStreamWaitEvent(k.sc, c->ev[EV_FRAME], 0)); // (the frame and the order flag)
   }
   HIPCK(c, hipGetLastError());
 
-  // ---- query order (second stream, after the frame): the kernels of both
-  // orders, each gated on the coherence test's flag (k_bbox's extra block) on the device — no host read.
-  // Forced orders enqueue only theirs; a small group (below kSmallGroup
-  // queries: its background and solutions stay in the Infinity Cache, where
-  // a numbering's locality matters little) takes the input order untested.
-  const int *flag = (const int *)c->oflag.p;
-#ifdef PMMG_HIP_MEASURE
-  if (c->set_order) hipLaunchKernelGGL(k_set_order, dim3(1), dim3(1), 0, s, st, force > 0 ? 1 : 0, c->bin_bits);
-#endif
-  // input order: the surface points in input order (stable compaction:
-  // per-block counts, their scan, the scatter; rocPRIM's select took 0.2 ms
-  // longer here, r03o)
-  // (EV_SB0 on its first kernel; EV_ORDER on its last with order_end; returns whether EV_ORDER was recorded)
-  auto launch_cls = [&](bool order_end) -> bool {
-    if (force == 1 || bg.nt <= 0) return false;
-    int *bc = (int *)c->cls_cnt.p;
-    hipExtLaunchKernelGGL(k_cls_count, dim3((unsigned)ncls), dim3(kBlock), 0, sb, c->ev[EV_SB0], nullptr, 0,
-                          pclass, (long long)np_new, (int)PMMG_PT_BDY, bc, flag, 0);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kBlock), 0, sb, bc, (int)ncls, &st->nbdy, flag, 0);
-    hipExtLaunchKernelGGL(k_cls_scatter, dim3((unsigned)ncls), dim3(kBlock), 0, sb, nullptr,
-                          order_end ? c->ev[EV_ORDER] : nullptr, 0, pclass, (long long)np_new, (int)PMMG_PT_BDY,
-                          (const int *)bc, order_b, flag, 0);
-    return order_end;
-  };
-  // Morton order: stable LSD radix sort of the keys (<= 3 * 7 + 2 bits) in 3 passes of 8 bits
-  // (pmmg_sort.hpp); the key kernel writes the first pass's digit table
-  auto launch_morton = [&]() -> int {
-    if (force == 0 || np_new <= 0) return 1;
-    const int ntile = (int)((np_new + kRsTile - 1) / kRsTile);
-    const long long nh = 256LL * ntile;
-    const int nch = (int)((nh + kScanChunk - 1) / kScanChunk);
-    if (!ensure(c, c->bvals2, 4 * nq) || !ensure(c, c->rs_hist, 4 * (size_t)nh) || !ensure(c, c->rs_csum, 4 * (size_t)nch))
-      return 0;
-    unsigned *k0 = (unsigned *)c->bkeys.p, *k1 = (unsigned *)c->bkeys2.p;
-    int *v0 = (int *)c->bvals.p, *v1 = (int *)c->bvals2.p, *hist = (int *)c->rs_hist.p, *csum = (int *)c->rs_csum.p;
-    const int tgrid = std::min(ntile, kRsGrid);
-    hipLaunchKernelGGL(k_bin_keys, dim3(tgrid), dim3(kBlock), 0, sc, xyz_new, pclass, np_new, (const Frame *)fr, flag,
-                       k0, v0, st, kRsTile, ntile, hist);
-    for (int pass = 0; pass < 3; pass++) {
-      const unsigned *kin = pass == 1 ? k1 : k0;
-      const int *vin = pass == 1 ? v1 : v0;
-      unsigned *kout = pass == 1 ? k0 : k1;
-      int *vout = pass == 1 ? v0 : (pass == 0 ? v1 : order_v);
-      if (pass > 0)
-        hipLaunchKernelGGL(k_rs_hist, dim3(tgrid), dim3(kBlock), 0, sc, kin, np_new, 8 * pass, ntile, hist, flag, 1);
-      hipLaunchKernelGGL(k_rs_scan_local, dim3(nch), dim3(kBlock), 0, sc, hist, (int)nh, csum, flag, 1);
-      hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kBlock), 0, sc, csum, nch, (int *)nullptr, flag, 1);
-      hipLaunchKernelGGL(k_rs_scan_add, dim3(nch), dim3(kBlock), 0, sc, hist, (int)nh, (const int *)csum, flag, 1);
-      hipLaunchKernelGGL(k_rs_scatter, dim3(tgrid), dim3(kBlock), 0, sc, kin, vin, np_new, 8 * pass, ntile,
-                         (const int *)hist, kout, vout, flag, 1);
-    }
-    hipLaunchKernelGGL(k_bin_split, dim3(blocks_for(np_new, 4096)), dim3(kBlock), 0, sc, (const int *)order_v, xyz_new,
-                       np_new, order_b, c->bin_qs ? (double *)c->qs.p : nullptr, (const DevStats *)st, flag);
-    return 1;
-  };
-  // one round of the grid for up to 1M surface points (static split: a
-  // second, nearly empty round doubled the surface branch alone)
-  unsigned long long *wt = nullptr;
-#ifdef PMMG_HIP_MEASURE
-  if (c->wave_time) {
-    const size_t nw = (size_t)8 * blocks_for((np_new + 7) / 8, c->bdy_bpx) * (kBlock / 64);
-    if (!ensure(c, c->wt, 32 * nw)) return 0;
-    HIPCK(c, hipMemsetAsync(c->wt.p, 0, 32 * nw, sb));
-    wt = (unsigned long long *)c->wt.p;
-    c->wt_n = nw;
+  // volume seeds
+  const long long nsamp = k.ng < bg.ne ? k.ng : bg.ne;
+  // kSeedBatch samples per thread in flight together (r05m: one per thread, the 8-way rank's 1.65M samples
+  // took 107 us — the grid's latency in rounds of waves — where cfg4's 12.6M take 262 us)
+  hipExtLaunchKernelGGL(k_seed_vol, dim3((blocks_for((nsamp + kSeedBatch - 1) / kSeedBatch, 8192) + 7) & ~7),
+                        dim3(kBlock), 0, s, nullptr, c->ev[EV_PREP], 0, bg, k.fr, k.grid, k.g, nsamp, kSeedLanes,
+                        (const int *)k.need);
+  HIPCK(c, hipGetLastError());
+  return 1;
+}
+
+// ---- order lists.  Input order: the surface points in input order (stable compaction: per-block counts, their
+// scan, the scatter; rocPRIM's select took 0.2 ms longer here, r03o), second stream.  Its kernels are gated on
+// the device flag: a large auto-order call launches them before its decision arrives.
+// (EV_SB0 on its first kernel; EV_ORDER on its last with order_end; returns whether EV_ORDER was recorded)
+static bool launch_cls(Call &k, bool order_end) {
+  pmmg_hip_ctx *c = k.c;
+  if (k.force == 1 || k.bg.nt <= 0) return false;
+  int *bc = (int *)c->cls_cnt.p;
+  hipExtLaunchKernelGGL(k_cls_count, dim3((unsigned)k.ncls), dim3(kBlock), 0, k.sb, c->ev[EV_SB0], nullptr, 0,
+                        k.pclass, (long long)k.np_new, (int)PMMG_PT_BDY, bc, k.flag, 0);
+  hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kBlock), 0, k.sb, bc, (int)k.ncls, &k.st->nbdy, k.flag, 0);
+  hipExtLaunchKernelGGL(k_cls_scatter, dim3((unsigned)k.ncls), dim3(kBlock), 0, k.sb, nullptr,
+                        order_end ? c->ev[EV_ORDER] : nullptr, 0, k.pclass, (long long)k.np_new, (int)PMMG_PT_BDY,
+                        (const int *)bc, k.order_b, k.flag, 0);
+  return order_end;
+}
+
+// Morton order: stable LSD radix sort of the keys (<= 3 * 7 + 2 bits) in 3 passes of 8 bits
+// (pmmg_sort.hpp); the key kernel writes the first pass's digit table
+static int launch_morton(Call &k) {
+  pmmg_hip_ctx *c = k.c;
+  const int np_new = k.np_new;
+  if (k.force == 0 || np_new <= 0) return 1;
+  hipStream_t sc = k.sc;
+  const size_t nq = (size_t)np_new;
+  const int ntile = (int)((np_new + kRsTile - 1) / kRsTile);
+  const long long nh = 256LL * ntile;
+  const int nch = (int)((nh + kScanChunk - 1) / kScanChunk);
+  if (!ensure(c, c->bvals2, 4 * nq) || !ensure(c, c->rs_hist, 4 * (size_t)nh) || !ensure(c, c->rs_csum, 4 * (size_t)nch))
+    return 0;
+  unsigned *k0 = (unsigned *)c->bkeys.p, *k1 = (unsigned *)c->bkeys2.p;
+  int *v0 = (int *)c->bvals.p, *v1 = (int *)c->bvals2.p, *hist = (int *)c->rs_hist.p, *csum = (int *)c->rs_csum.p;
+  const int tgrid = std::min(ntile, kRsGrid);
+  hipLaunchKernelGGL(k_bin_keys, dim3(tgrid), dim3(kBlock), 0, sc, k.xyz_new, k.pclass, np_new, (const Frame *)k.fr,
+                     k.flag, k0, v0, k.st, kRsTile, ntile, hist);
+  for (int pass = 0; pass < 3; pass++) {
+    const unsigned *kin = pass == 1 ? k1 : k0;
+    const int *vin = pass == 1 ? v1 : v0;
+    unsigned *kout = pass == 1 ? k0 : k1;
+    int *vout = pass == 1 ? v0 : (pass == 0 ? v1 : k.order_v);
+    if (pass > 0)
+      hipLaunchKernelGGL(k_rs_hist, dim3(tgrid), dim3(kBlock), 0, sc, kin, np_new, 8 * pass, ntile, hist, k.flag, 1);
+    hipLaunchKernelGGL(k_rs_scan_local, dim3(nch), dim3(kBlock), 0, sc, hist, (int)nh, csum, k.flag, 1);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kBlock), 0, sc, csum, nch, (int *)nullptr, k.flag, 1);
+    hipLaunchKernelGGL(k_rs_scan_add, dim3(nch), dim3(kBlock), 0, sc, hist, (int)nh, (const int *)csum, k.flag, 1);
+    hipLaunchKernelGGL(k_rs_scatter, dim3(tgrid), dim3(kBlock), 0, sc, kin, vin, np_new, 8 * pass, ntile,
+                       (const int *)hist, kout, vout, k.flag, 1);
   }
-#endif
-  // k_bdy's blocks: kBlock threads, or one wave each (bdy_wave), so that they fit into the single-wave
-  // slots the volume kernel's one-wave blocks leave while it runs beside them
-  const int bdy_tpb = c->bdy_wave ? 64 : kBlock;
-  const auto bdy_fn = map_src ? k_bdy<1> : k_bdy<0>;
-  auto bdy = [&](int want) {
-    hipLaunchKernelGGL(bdy_fn, dim3(8 * blocks_for((np_new + 7) / 8, c->bdy_bpx) * (kBlock / bdy_tpb)), dim3(bdy_tpb),
-                       0, sb, bg,
-                       (const Frame *)fr, (const unsigned long long *)sgrid, gs, xyz_new, (const int *)order_b, S, elem_out,
-                       hit_out, (int *)c->fb_bdy.p, st, c->maxstep, c->bdy_dyn, FbInit{(int *)c->bbest.p},
-                       FbGridBufs{(int *)c->fbg_bdy_c.p, (int *)c->fbg_bdy_u.p, (int *)c->fbg_bdy_i.p}, flag, want, wt, ma);
-  };
-  // ---- surface branch (second stream, after the order): seeds, k_bdy
-  // (r05ae: the surface seeds moved before the wait for the volume seed grid, beside it: preparation
-  // +0.03 ms at cfg4, +0.17 for the Mmg-like numbering, the 8-way rank +0.04 — not kept)
-  auto srf_head = [&]() {
-    if (c->srf_solo > 0 || (c->srf_solo < 0 && np_new >= kSmallGroup))
-      HIPCK(c, hipStreamWaitEvent(sb, c->ev[EV_PREP], 0));
-    if (bg.nt <= 0) HIPCK(c, hipEventRecord(c->ev[EV_BDY0], sb)); // (else the start of the surface seeds)
-    if (bg.nt > 0) {
-      if (force == 0) HIPCK(c, hipStreamWaitEvent(sb, c->ev[EV_FRAME], 0)); // (the surface seeds need the frame)
-      hipExtLaunchKernelGGL(k_seed_srf, dim3(blocks_for(bg.nt, 4096) * (kBlock / bdy_tpb)), dim3(bdy_tpb), 0, sb,
-                            c->ev[EV_BDY0], nullptr, 0, bg, (const Frame *)fr, sgrid, gs,
-                            need ? (const int *)need + 1 : (const int *)nullptr);
-      if (c->vol_wait_seed) HIPCK(c, hipEventRecord(c->ev[EV_SRFSEED], sb));
+  hipLaunchKernelGGL(k_bin_split, dim3(blocks_for(np_new, 4096)), dim3(kBlock), 0, sc, (const int *)k.order_v,
+                     k.order_b, (const DevStats *)k.st, k.flag);
+  return 1;
+}
+
+// ---- surface branch (second stream): seeds, k_bdy, its fallbacks, the surface grid's refill
+// (r05ae: the surface seeds moved before the wait for the volume seed grid, beside it: preparation
+// +0.03 ms at cfg4, +0.17 for the Mmg-like numbering, the 8-way rank +0.04 — not kept)
+static int srf_head(Call &k) {
+  pmmg_hip_ctx *c = k.c;
+  const Bg &bg = k.bg;
+  // a large call's surface branch waits for the volume seed grid (r04zo, cfg4: the seed grid ran at 455 instead
+  // of 261 us beside k_bdy; step 4.24 -> 4.13 ms, Mmg-like 5.01 -> 4.93, shuffled =)
+  if (k.np_new >= kSmallGroup) HIPCK(c, hipStreamWaitEvent(k.sb, c->ev[EV_PREP], 0));
+  if (bg.nt <= 0) HIPCK(c, hipEventRecord(c->ev[EV_BDY0], k.sb)); // (else the start of the surface seeds)
+  if (bg.nt > 0) {
+    if (k.force == 0) HIPCK(c, hipStreamWaitEvent(k.sb, c->ev[EV_FRAME], 0)); // (the surface seeds need the frame)
+    hipExtLaunchKernelGGL(k_seed_srf, dim3(blocks_for(bg.nt, 4096)), dim3(kBlock), 0, k.sb, c->ev[EV_BDY0], nullptr,
+                          0, bg, (const Frame *)k.fr, k.sgrid, k.gs,
+                          k.need ? (const int *)k.need + 1 : (const int *)nullptr);
+  }
+  return 1;
+}
+
+// one round of the grid for up to 1M surface points (static split: a
+// second, nearly empty round doubled the surface branch alone)
+static void launch_bdy(Call &k) {
+  pmmg_hip_ctx *c = k.c;
+  const auto bdy_fn = k.ma.src ? k_bdy<1> : k_bdy<0>;
+  hipLaunchKernelGGL(bdy_fn, dim3(8 * blocks_for((k.np_new + 7) / 8, kBdyBpx)), dim3(kBlock), 0,
+                     k.sb, k.bg, (const Frame *)k.fr, (const unsigned long long *)k.sgrid, k.gs, k.xyz_new,
+                     (const int *)k.order_b, k.S, k.elem_out, k.hit_out, (int *)c->fb_bdy.p, k.st, c->maxstep,
+                     FbInit{(int *)c->bbest.p},
+                     FbGridBufs{(int *)c->fbg_bdy_c.p, (int *)c->fbg_bdy_u.p, (int *)c->fbg_bdy_i.p}, k.ma);
+}
+
+static int srf_tail(Call &k) {
+  pmmg_hip_ctx *c = k.c;
+  bool rec = false; // EV_BDY1 recorded by the branch's last launch
+  const bool fill = k.nsg >= kRefillCells;
+  if (k.bg.nt > 0) {
+    hipLaunchKernelGGL(k_fb_grid, dim3(1), dim3(kBlock), 0, k.sb, k.xyz_new, (const int *)c->fb_bdy.p, k.st, 1,
+                       FbGridBufs{(int *)c->fbg_bdy_c.p, (int *)c->fbg_bdy_u.p, (int *)c->fbg_bdy_i.p});
+    launch_bdy_fallbacks(c, k.sb, k.S, k.xyz_new, k.elem_out, k.hit_out, fill ? nullptr : c->ev[EV_BDY1]);
+    rec = !fill;
+    HIPCK(c, hipGetLastError());
+    if (fill) { // the surface grid refilled for the next call (see k_reset)
+      hipExtLaunchKernelGGL(k_fill64, dim3(blocks_for((k.nsg + 1) / 2, 2048)), dim3(kBlock), 0, k.sb, nullptr,
+                            c->ev[EV_BDY1], 0, k.sgrid, k.nsg, ~0ULL);
+      rec = true;
+      c->sgrid_clean_p = c->sgrid.p;
+      c->sgrid_clean_n = k.nsg;
     }
-    return 1;
-  };
-  auto srf_tail = [&]() {
-    bool rec = false; // EV_BDY1 recorded by the branch's last launch
-    const bool fill = nsg >= kRefillCells;
-    if (bg.nt > 0) {
-      if (!c->no_fb) {
-        hipLaunchKernelGGL(k_fb_grid, dim3(1), dim3(bdy_tpb), 0, sb, xyz_new, (const int *)c->fb_bdy.p, st, 1,
-                           FbGridBufs{(int *)c->fbg_bdy_c.p, (int *)c->fbg_bdy_u.p, (int *)c->fbg_bdy_i.p});
-        // one-wave surface branch: its exhaustive kernels (blocks of kBlock threads, which a running volume
-        // kernel's one-wave blocks would keep waiting for four free slots) run on the main stream after the
-        // volume ones
-        if (c->bdy_wave) HIPCK(c, hipEventRecord(c->ev[EV_BDYFB], sb));
-        else launch_bdy_fallbacks(c, sb, S, xyz_new, elem_out, hit_out, fill ? nullptr : c->ev[EV_BDY1]);
-        rec = !c->bdy_wave && !fill;
-      }
-      HIPCK(c, hipGetLastError());
-      if (fill) { // the surface grid refilled for the next call (see k_reset above)
-        hipExtLaunchKernelGGL(k_fill64, dim3(blocks_for((nsg + 1) / 2, 2048) * (kBlock / bdy_tpb)), dim3(bdy_tpb), 0,
-                              sb, nullptr, c->ev[EV_BDY1], 0, sgrid, nsg, ~0ULL);
-        rec = true;
-        c->sgrid_clean_p = c->sgrid.p;
-        c->sgrid_clean_n = nsg;
-      }
-    }
-    if (!rec) HIPCK(c, hipEventRecord(c->ev[EV_BDY1], sb));
-    return 1;
-  };
-  // ---- volume (main stream): walk + exact test + interpolation in one
-  // kernel, then the exact continuation of the few queries it did not settle
-  const bool fuse_cont = c->fuse_cont && !vsplit;
-  const ContArgs ca{(int *)c->fb_vol.p, FbInit{(int *)c->best.p}, c->maxstep, fuse_cont ? 1 : 0};
-  // (stop: an event the launch records, EV_WALK when it is the call's only volume launch)
-  auto vol = [&](int want, hipEvent_t stop) {
-    // (measurement build; a plain call: HIPCK's `return 0` would give this void lambda a return type)
-    if (c->vol_wait_seed && bg.nt > 0 && want <= 0) (void)hipStreamWaitEvent(s, c->ev[EV_SRFSEED], 0);
-    const int nb = (np_new + 63) / 64;
-    if (!vsplit) {
-      hipExtLaunchKernelGGL(vol_fn, dim3(nb), dim3(64), 0, s, nullptr, stop, 0, bg, (const Frame *)fr,
-                            (const unsigned long long *)grid, g, xyz_new, pclass, (const int *)order_v,
-                            c->bin_qs ? (const double *)c->qs.p : nullptr, np_new, (ContEntry *)c->cont.p, st, S,
-                            elem_out, hit_out, c->filter_steps, flag, c->xcd_run, c->pad, want, lb, 0, ca, ma);
-      return;
-    }
-    // split stage: walk chunk j (main stream), then its interpolation on stream_i, beside walk chunk j + 1
-    // (chunks of whole XCD runs)
-    const int run = 8 * std::max(1, c->xcd_run);
-    const int per = std::max(run, (nb + c->vol_chunks - 1) / c->vol_chunks / run * run);
-    const int ixr = c->ixcd_run >= 0 ? c->ixcd_run : c->xcd_run;
-    const int w = want > 0 ? 1 : 0;
-    for (int j = 0, b0 = 0; b0 < nb; j++, b0 += per) {
-      const int nbj = std::min(per, nb - b0);
-      hipLaunchKernelGGL(vol_fn, dim3(nbj), dim3(64), 0, s, bg, (const Frame *)fr, (const unsigned long long *)grid,
-                         g, xyz_new, pclass, (const int *)order_v, c->bin_qs ? (const double *)c->qs.p : nullptr,
-                         np_new, (ContEntry *)c->cont.p, st, S, elem_out, hit_out, c->filter_steps, flag,
-                         c->xcd_run, c->pad, want, lb, b0, ca, ma);
-      hipEvent_t ej = c->ev_chunk[w][std::min(j, (int)pmmg_hip_ctx::kMaxVolChunks - 1)];
-      (void)hipEventRecord(ej, s);
-      (void)hipStreamWaitEvent(c->stream_i, ej, 0);
-      hipLaunchKernelGGL(vpick.ifn, dim3(nbj), dim3(64), 0, c->stream_i, lb, (const int *)order_v,
-                         (const DevStats *)st, np_new, S, flag, ixr, want, b0);
-    }
-  };
-  // host_order: the launches that do not depend on the order (the input order's surface list, gated on the
-  // device flag; the surface seeds) go out before the host waits for the decision, so that after it only the
-  // chosen order's kernels are enqueued, the volume kernel first (r06ze: the device idled ~20 us between the
+  }
+  if (!rec) HIPCK(c, hipEventRecord(c->ev[EV_BDY1], k.sb));
+  return 1;
+}
+
+// ---- volume stage (main stream): walk + exact test and continuation + interpolation in one kernel, whose
+// dispatch records EV_WALK.  It reads the order branch's lists only in Morton order; in input order its queries
+// are the input's volume points and there is nothing to wait for (r05: the cross-stream wait was ~20 us of a
+// small group's main chain): launched right after the seed grid, the stage opens at EV_PREP
+static int launch_vol(Call &k) {
+  pmmg_hip_ctx *c = k.c;
+  if (k.force != 0 && k.sc != k.sb) HIPCK(c, hipStreamWaitEvent(k.s, c->ev[EV_ORDER2], 0));
+  c->ev_vol0 = k.force == 0 ? EV_PREP : EV_VOL0;
+  if (c->ev_vol0 == EV_VOL0) HIPCK(c, hipEventRecord(c->ev[EV_VOL0], k.s));
+  const ContArgs ca{(int *)c->fb_vol.p, FbInit{(int *)c->best.p}, c->maxstep};
+  hipExtLaunchKernelGGL(k.vol_fn, dim3((k.np_new + 63) / 64), dim3(64), 0, k.s, nullptr, c->ev[EV_WALK], 0, k.bg,
+                        (const Frame *)k.fr, (const unsigned long long *)k.grid, k.g, k.xyz_new, k.pclass,
+                        (const int *)k.order_v, k.np_new, k.st, k.S, k.elem_out, k.hit_out, c->filter_steps, k.flag,
+                        kXcdRun, ca, k.ma);
+  return 1;
+}
+
+// ---- tail (main stream): the volume grid's refill, the volume queries' exhaustive fallbacks, the join
+static int launch_tail(Call &k) {
+  pmmg_hip_ctx *c = k.c;
+  hipStream_t s = k.s;
+  // the volume seed grid refilled for the next call as soon as the volume kernel is done with it, on its own
+  // stream beside the main stream's tail (the fallbacks: latency-bound) and the surface stream's; r06: at the
+  // end of the main stream it added ~36 us to a cfg4 call (r05ao: on the surface stream right after the volume
+  // kernel it ran behind k_bdy's tail instead)
+  const bool refill = k.ng >= kRefillCells;
+  if (refill) {
+    if (!c->stream_f) HIPCK(c, hipStreamCreateWithFlags(&c->stream_f, hipStreamNonBlocking));
+    HIPCK(c, hipStreamWaitEvent(c->stream_f, c->ev[EV_WALK], 0));
+    hipExtLaunchKernelGGL(k_fill64, dim3(blocks_for((k.ng + 1) / 2, 2048)), dim3(kBlock), 0, c->stream_f, nullptr,
+                          c->ev[EV_FILL], 0, k.grid, k.ng, ~0ULL);
+    HIPCK(c, hipGetLastError());
+    c->grid_clean_p = c->grid.p;
+    c->grid_clean_n = k.ng;
+  }
+  HIPCK(c, hipGetLastError());
+  // exhaustive fallbacks of the volume queries (lists and counts on the
+  // device; the surface ones ran on the surface stream after k_bdy): the
+  // list's query grid, then the searches, the last of which records EV_JOIN
+  hipLaunchKernelGGL(k_fb_grid, dim3(1), dim3(kBlock), 0, s, k.xyz_new, (const int *)c->fb_vol.p, k.st, 0,
+                     FbGridBufs{(int *)c->fbg_vol_c.p, (int *)c->fbg_vol_u.p, (int *)c->fbg_vol_i.p});
+  launch_vol_fallbacks(c, k.S, k.xyz_new, k.elem_out, k.hit_out, c->ev[EV_JOIN]);
+  HIPCK(c, hipGetLastError());
+  HIPCK(c, hipStreamWaitEvent(s, c->ev[EV_BDY1], 0));
+  if (refill) HIPCK(c, hipStreamWaitEvent(s, c->ev[EV_FILL], 0));
+  HIPCK(c, hipEventRecord(c->ev[EV_END], s));
+  c->pending = true;
+  return 1;
+}
+
+static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const uint8_t *pclass, double *met_out,
+                      double *const *fields_out, int *elem_out, int8_t *hit_out, double *rec_out = nullptr,
+                      const int *map_src = nullptr) {
+  Call k{};
+  k.c = c;
+  k.np_new = np_new;
+  k.xyz_new = xyz_new;
+  k.pclass = pclass;
+  k.elem_out = elem_out;
+  k.hit_out = hit_out;
+  k.bg = c->bg;
+  k.s = c->stream;
+  k.sb = k.sc = c->stream2;
+  if (!call_slots(k, met_out, fields_out, rec_out, map_src) || !call_scratch(k) || !launch_frame_seeds(k)) return 0;
+  // A large auto-order call: the launches that do not depend on the order (the input order's surface list, gated
+  // on the device flag; the surface seeds) go out before the host waits for the decision, so that after it only
+  // the chosen order's kernels are enqueued, the volume kernel first (r06ze: the device idled ~20 us between the
   // seed grid and the volume kernel of an 8-way rank while the host enqueued ~10 launches ahead of it)
-  const bool pre = host_order;
+  const bool pre = k.force < 0;
+  bool ord = false; // EV_ORDER recorded
   if (pre) {
-    if (!launch_cls(true)) HIPCK(c, hipEventRecord(c->ev[EV_ORDER], sb));
-    if (!srf_head()) return 0;
+    if (!launch_cls(k, true)) HIPCK(c, hipEventRecord(c->ev[EV_ORDER], k.sb));
+    ord = true;
+    if (!srf_head(k)) return 0;
     HIPCK(c, hipGetLastError());
     // the decision, written by k_bbox's last block (coherence_final); from here on a forced order
     HIPCK(c, hipEventSynchronize(c->ev[EV_FRAME]));
@@ -1887,134 +1678,26 @@ static int run_device(pmmg_hip_ctx *c, int np_new, const double *xyz_new, const 
       set_err(c, "locate_interp: the query order decision did not arrive (%d)", f);
       return 0;
     }
-    force = f;
-    split = false; // (the order is known: only its kernels are enqueued, no gated launches of the other)
-  }
-  if (split) {
-    // Host enqueue order (r05q trace): the input order's kernels first — the surface list, the surface
-    // seeds and walk, the volume kernel — then the ~19 binning launches and the Morton order's launches.
-    // Enqueued after the binning chain, the input order's volume kernel started ~200 us after the seed grid
-    // had finished: the host was still enqueueing (~8 us per launch), the device idle.
-    if (!launch_cls(true)) HIPCK(c, hipEventRecord(c->ev[EV_ORDER], sb));
-    if (!srf_head()) return 0;
-    if (bg.nt > 0) bdy(0);
-    c->ev_vol0 = EV_VOL0;
-    HIPCK(c, hipEventRecord(c->ev[EV_VOL0], s));
-    vol(0, nullptr);
-    if (!launch_morton()) return 0;
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipEventRecord(c->ev[EV_ORDER2], sc));
-    if (bg.nt > 0) {
-      HIPCK(c, hipStreamWaitEvent(sb, c->ev[EV_ORDER2], 0));
-      bdy(1);
-    }
-    if (!srf_tail()) return 0;
-    HIPCK(c, hipStreamWaitEvent(s, c->ev[EV_ORDER2], 0));
-    vol(1, nullptr);
+    k.force = f;
   } else {
-    // (EV_ORDER on the surface list's last kernel unless the Morton lists may follow on the same stream;
-    // EV_ORDER2 is waited for only when the order is Morton)
-    const bool ord = !pre && launch_cls(force == 0);
-    if (!launch_morton()) return 0;
-    HIPCK(c, hipGetLastError());
-    if (!pre && !ord) HIPCK(c, hipEventRecord(c->ev[EV_ORDER], sb));
-    if (force != 0) HIPCK(c, hipEventRecord(c->ev[EV_ORDER2], sc)); // (sc == sb: the same point)
-    // the volume kernel reads the order branch's lists only in Morton order (or when it may be chosen); in
-    // forced input order its queries are the input's volume points and the wait is dropped (r05: the
-    // cross-stream wait was ~20 us of a small group's main chain)
-    bool vol_first = pre && !c->bdy_first;
-#ifdef PMMG_HIP_MEASURE
-    vol_first = vol_first && c->brick <= 0;
-#endif
-    // the volume kernel right after the seed grid (input order, nothing to wait for, nothing launched on the
-    // main stream in between): the stage opens at EV_PREP
-    bool vol_direct = force == 0 && !c->bdy_first;
-#ifdef PMMG_HIP_MEASURE
-    vol_direct = vol_direct && c->brick <= 0 && !c->set_order && !c->quant_side;
-#endif
-    c->ev_vol0 = vol_direct ? EV_PREP : EV_VOL0;
-    auto vol_main = [&]() {
-      if (force < 0) (void)hipStreamWaitEvent(s, c->ev[EV_ORDER], 0);
-      if (force != 0 && sc != sb) (void)hipStreamWaitEvent(s, c->ev[EV_ORDER2], 0);
-      if (c->bdy_first) (void)hipStreamWaitEvent(s, c->ev[EV_BDY1], 0);
-      if (c->ev_vol0 == EV_VOL0) (void)hipEventRecord(c->ev[EV_VOL0], s);
-      vol(-1, vsplit ? nullptr : c->ev[EV_WALK]);
-    };
-    if (vol_first) vol_main();
-    if (sc != sb && force != 0) HIPCK(c, hipStreamWaitEvent(sb, c->ev[EV_ORDER2], 0)); // the Morton surface list
-    if (!pre && !srf_head()) return 0;
-    if (c->bdy_after && vol_first) HIPCK(c, hipStreamWaitEvent(sb, c->ev[EV_WALK], 0));
-    if (bg.nt > 0) bdy(-1);
-    if (!srf_tail()) return 0;
-#ifdef PMMG_HIP_MEASURE
-    if (c->brick > 0 && !brick_renumber(c, s, bg, S, fr, g)) return 0;
-#endif
-    if (!vol_first) vol_main();
-    HIPCK(c, hipGetLastError());
+    ord = launch_cls(k, k.force == 0);
   }
-  if (split || vsplit) HIPCK(c, hipEventRecord(c->ev[EV_WALK], s)); // (else recorded by the volume launch)
-  // the volume seed grid refilled for the next call as soon as the volume kernel is done with it, on its own
-  // stream beside the main stream's tail (the exact continuation, the fallbacks: latency-bound) and the
-  // surface stream's; r06: at the end of the main stream it added ~36 us to a cfg4 call (r05ao: on the
-  // surface stream right after the volume kernel it ran behind k_bdy's tail instead)
-  const bool refill = ng >= kRefillCells;
-  if (refill) {
-    if (!c->stream_f) HIPCK(c, hipStreamCreateWithFlags(&c->stream_f, hipStreamNonBlocking));
-    HIPCK(c, hipStreamWaitEvent(c->stream_f, c->ev[EV_WALK], 0));
-    hipExtLaunchKernelGGL(k_fill64, dim3(blocks_for((ng + 1) / 2, 2048)), dim3(kBlock), 0, c->stream_f, nullptr,
-                          c->ev[EV_FILL], 0, grid, ng, ~0ULL);
-    HIPCK(c, hipGetLastError());
-    c->grid_clean_p = c->grid.p;
-    c->grid_clean_n = ng;
-  }
-  // (8 x 64 one-wave blocks for a large call; fewer for a small group, whose continuations are a few hundred)
-  const int wx = (int)std::min<long long>(64, std::max<long long>(2, (long long)np_new / 65536));
-  if (!fuse_cont) // (continued inside the volume kernel otherwise: ContArgs)
-    hipLaunchKernelGGL(k_vol_walk_exact, dim3(8 * wx), dim3(64), 0, s, bg, xyz_new, (int *)c->fb_vol.p,
-                       (const ContEntry *)c->cont.p, st, S, elem_out, hit_out, c->maxstep, FbInit{(int *)c->best.p},
-                       FbGridBufs{(int *)c->fbg_vol_c.p, (int *)c->fbg_vol_u.p, (int *)c->fbg_vol_i.p});
+  // the chosen order's lists (EV_ORDER2 is waited for only when the order is Morton)
+  if (!launch_morton(k)) return 0;
   HIPCK(c, hipGetLastError());
-  if (vsplit) { // the volume stage ends with the interpolation's last chunk
-    HIPCK(c, hipEventRecord(c->ev_interp, c->stream_i));
-    HIPCK(c, hipStreamWaitEvent(s, c->ev_interp, 0));
-  }
-  c->ev_vol = (fuse_cont && !vsplit) ? EV_WALK : EV_VOL;
-  if (c->ev_vol == EV_VOL) HIPCK(c, hipEventRecord(c->ev[EV_VOL], s));
-  // ---- exhaustive fallbacks of the volume queries (lists and counts on the
-  // device; the surface ones ran on the surface stream after k_bdy): the
-  // list's query grid, then the searches
-  const bool bdy_fb_main = !c->no_fb && c->bdy_wave && bg.nt > 0;
-  if (!c->no_fb) {
-    hipLaunchKernelGGL(k_fb_grid, dim3(1), dim3(kBlock), 0, s, xyz_new, (const int *)c->fb_vol.p, st, 0,
-                       FbGridBufs{(int *)c->fbg_vol_c.p, (int *)c->fbg_vol_u.p, (int *)c->fbg_vol_i.p});
-    launch_vol_fallbacks(c, S, xyz_new, elem_out, hit_out, bdy_fb_main ? nullptr : c->ev[EV_JOIN]);
-  }
-  if (bdy_fb_main) {
-    HIPCK(c, hipStreamWaitEvent(s, c->ev[EV_BDYFB], 0));
-    launch_bdy_fallbacks(c, s, S, xyz_new, elem_out, hit_out);
-  }
+  if (!ord) HIPCK(c, hipEventRecord(c->ev[EV_ORDER], k.sb));
+  if (k.force != 0) HIPCK(c, hipEventRecord(c->ev[EV_ORDER2], k.sc)); // (sc == sb: the same point)
+  if (pre && !launch_vol(k)) return 0;
+  if (k.sc != k.sb && k.force != 0) HIPCK(c, hipStreamWaitEvent(k.sb, c->ev[EV_ORDER2], 0)); // the Morton surface list
+  if (!pre && !srf_head(k)) return 0;
+  if (k.bg.nt > 0) launch_bdy(k);
+  if (!srf_tail(k)) return 0;
+  if (!pre && !launch_vol(k)) return 0;
   HIPCK(c, hipGetLastError());
-  if (c->no_fb || bdy_fb_main) HIPCK(c, hipEventRecord(c->ev[EV_JOIN], s)); // (else the last fallback's stop)
-  HIPCK(c, hipStreamWaitEvent(s, c->ev[EV_BDY1], 0));
-  if (refill) HIPCK(c, hipStreamWaitEvent(s, c->ev[EV_FILL], 0));
-  HIPCK(c, hipEventRecord(c->ev[EV_END], s));
-  c->pending = true;
-  return 1;
+  return launch_tail(k);
 }
 
 static int collect_stats(pmmg_hip_ctx *c, pmmg_hip_stats *out) {
-#ifdef PMMG_HIP_MEASURE
-  if (c->wave_time && c->wt_n) { // k_bdy's per-wave records of the call, appended to PMMG_HIP_WAVETIME_OUT
-    std::vector<unsigned long long> w(4 * c->wt_n);
-    HIPCK(c, ctx_d2h(c, w.data(), c->wt.p, 8 * w.size()));
-    const char *path = getenv("PMMG_HIP_WAVETIME_OUT");
-    if (FILE *f = path ? fopen(path, "ab") : nullptr) {
-      fwrite(w.data(), 8, w.size(), f);
-      fclose(f);
-    }
-    c->wt_n = 0;
-  }
-#endif
   DevStats h;
   int order[2] = {0, 0}; // the call's query order, decided on the device
   HIPCK(c, ctx_d2h(c, order, c->oflag.p, sizeof(order)));
@@ -2062,13 +1745,11 @@ static int collect_stats(pmmg_hip_ctx *c, pmmg_hip_stats *out) {
   out->ms_prepare = ms;
   HIPCK(c, hipEventElapsedTime(&ms, c->ev[EV_SB0], c->ev[EV_ORDER]));
   out->ms_sort = ms; // on the second (and third) stream, concurrent with the seed grid
-  HIPCK(c, hipEventElapsedTime(&ms, c->ev[c->ev_vol0], c->ev[c->ev_vol]));
-  out->ms_vol = ms;
   HIPCK(c, hipEventElapsedTime(&ms, c->ev[c->ev_vol0], c->ev[EV_WALK]));
-  out->ms_vol_locate = ms;
+  out->ms_vol = out->ms_vol_locate = ms; // (one kernel locates and interpolates: the same interval)
   HIPCK(c, hipEventElapsedTime(&ms, c->ev[EV_BDY0], c->ev[EV_BDY1]));
   out->ms_bdy = ms; // on the surface stream, concurrent with the volume kernels
-  HIPCK(c, hipEventElapsedTime(&ms, c->ev[c->ev_vol], c->ev[EV_JOIN]));
+  HIPCK(c, hipEventElapsedTime(&ms, c->ev[EV_WALK], c->ev[EV_JOIN]));
   out->ms_fallback = ms; // the volume queries' exhaustive search (the surface one is in ms_bdy)
   HIPCK(c, hipEventElapsedTime(&ms, c->ev[EV_START], c->ev[EV_END]));
   out->ms_total = ms;
@@ -2384,25 +2065,15 @@ static void stats_sum(pmmg_hip_stats *a, const pmmg_hip_stats &b) {
 static pmmg_hip_ctx *group_lane(pmmg_hip_ctx *c, int j) {
   while ((int)c->lanes.size() <= j) {
     const bool first = c->lanes.empty();
-    pmmg_hip_ctx *l = create_ctx(c->device, c->options, false, first && c->lane0 ? c : nullptr);
+    pmmg_hip_ctx *l = create_ctx(c->device, c->options, first ? c : nullptr);
     if (!l) {
       set_err(c, "locate_interp_groups: cannot create group lane %d", (int)c->lanes.size());
       return nullptr;
     }
-    if (c->lane_streams == 1 && !l->borrowed_streams) {
+    if (!l->borrowed_streams) { // one stream per lane (pmmg_hip_ctx::group_lanes: the hardware's 4 queues)
       (void)hipStreamDestroy(l->stream2);
       l->stream2 = l->stream;
     }
-#ifdef PMMG_HIP_MEASURE
-    if (c->lane_streams == 3 && !l->borrowed_streams) { // both of a lane's streams at the highest priority
-      int lo = 0, hi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-      (void)hipStreamDestroy(l->stream);
-      (void)hipStreamDestroy(l->stream2);
-      (void)hipStreamCreateWithPriority(&l->stream, hipStreamNonBlocking, hi);
-      (void)hipStreamCreateWithPriority(&l->stream2, hipStreamNonBlocking, hi);
-    }
-#endif
     c->lanes.push_back(l);
   }
   return c->lanes[j];
@@ -2447,11 +2118,6 @@ int pmmg_hip_locate_interp_groups(pmmg_hip_ctx *c, int ngroup, const pmmg_hip_gr
   }
   HIPCK(c, hipSetDevice(c->device));
   if (!snap_join(c)) return 0;
-  if (c->stream2_hi) { // (see run_device)
-    HIPCK(c, hipStreamSynchronize(c->stream2_hi));
-    HIPCK(c, hipStreamDestroy(c->stream2_hi));
-    c->stream2_hi = nullptr;
-  }
   // a large call's extra streams (binning, refill) are released before the lanes take theirs, so that the
   // lanes' streams find the queues those held (a later large call creates them again)
   for (hipStream_t *x : {&c->stream3, &c->stream_f})

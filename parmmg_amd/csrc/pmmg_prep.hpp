@@ -2,10 +2,10 @@
 // (included by pmmg_hip.hip only): state reset, background frame, volume and
 // surface seed grids, and the query order.
 //
-// The input-order coherence test runs on the device (in k_bbox: coherence_final's flag); in
-// auto mode both the Morton binning (pmmg_sort.hpp) and the class compaction
-// of the surface list are enqueued, each gated on that flag, and the volume
-// kernel reads it: nothing is read back inside a call.
+// The input-order coherence test runs on the device (in k_bbox: coherence_final's flag,
+// which a large auto-order call also reads back once, run_device); the Morton
+// binning (pmmg_sort.hpp) and the class compaction of the surface list are
+// gated on that flag, and the volume kernel reads it.
 #pragma once
 
 #include "pmmg_device.hpp"
@@ -20,17 +20,11 @@ namespace pmmg {
 struct DevStats {
   int nvol, nbdy;       // query counts (nvol: Morton path only; the input-order walk counts its own)
   int nfb_vol, nfb_bdy; // fallback lists (exhaustive searches)
-  int ncont;            // walks continued in exact arithmetic (k_vol_walk_exact)
-  int sorted;           // 1: queries Morton-binned, 0: input order (coherent numbering)
-  int bin_bits;         // Morton bits per axis of the binning keys (read back with `sorted`)
-  int pad;
-  int bdy_next[8];      // k_bdy: per-XCD work counters (the next unclaimed surface query of each eighth)
   int nac_vol, nac_bdy; // fallback queries no element accepted (the closest searches' lists)
   // uniform grids over each fallback list's queries (fb_grid_build): origin,
   // inverse cell size, cells per axis (0: not built)
   double fbg_lo[2][3], fbg_inv[2][3];
   int fbg_n[2];
-  unsigned walk_done;   // k_vol_walk_exact blocks done (its last block builds the volume list's grid)
   unsigned bdy_done;    // k_bdy blocks done (the surface list's grid)
   unsigned fb_done[4];  // blocks done with an exhaustive kernel (volume accept / closest, surface accept /
                         // closest): the last one finishes
@@ -222,19 +216,10 @@ __device__ __forceinline__ void axis_hist_block(int (*h)[kMapBins], const double
 // launch: both need only the frame (r05: one launch and its gap less per call;
 // the grid is at least kHistBlocks blocks).
 constexpr int kQuantU = 4;
-// The axis histograms alone (kHistBlocks blocks): a large call's seed grid
-// then needs only them and the frame, while the fixed-point copy runs on a
-// stream of its own beside it (r06, run_device: quant_side)
-__global__ __launch_bounds__(kBlock) void k_axis_hist(const double *xyz, long long np, const Frame *fr, int hstride,
-                                                      int *H) {
-  __shared__ int h[3][kMapBins];
-  axis_hist_block(h, xyz, np, fr, hstride, H);
-}
-
 __global__ __launch_bounds__(kBlock) void k_quantize(const double *xyz, long long np, const Frame *fr, int *xq,
                                                      int hstride, int *H) {
   __shared__ int h[3][kMapBins];
-  if (H && blockIdx.x < kHistBlocks) axis_hist_block(h, xyz, np, fr, hstride, H); // (block-uniform)
+  if (blockIdx.x < kHistBlocks) axis_hist_block(h, xyz, np, fr, hstride, H); // (block-uniform)
   const long long nth = (long long)gridDim.x * blockDim.x;
   if (kXqStride == 3 && ((uintptr_t)xyz & 15) == 0 && ((uintptr_t)xq & 7) == 0) {
     const double qs = fr->qs, qc0 = fr->qc[0], qc1 = fr->qc[1], qc2 = fr->qc[2];
@@ -461,8 +446,7 @@ constexpr int kSeedBatch = 3;
 // need != null (a call with a point map): the count of volume queries the map
 // gives no start (k_map_count); the grid is not filled when it is zero.
 __global__ __launch_bounds__(kBlock) void k_seed_vol(Bg bg, Frame *fr, unsigned long long *cell, int g,
-                                                     long long nsamp, int lanes, int v0only, const double *xyzc,
-                                                     const int *need) {
+                                                     long long nsamp, int lanes, const int *need) {
   if (need && *need == 0) return;
   constexpr int R = kSeedRun, B = kSeedBatch;
   __shared__ int smin;
@@ -505,32 +489,12 @@ __global__ __launch_bounds__(kBlock) void k_seed_vol(Bg bg, Frame *fr, unsigned 
       }
     }
     long long sq[B][3]; // 64-bit: clamped coordinates (+-2^30) of vertices outside the sampled frame
-    double cc[B][3];    // (xyzc: the centroids in fp64)
 #pragma unroll
     for (int b = 0; b < B; b++) {
       ok[b] = ok[b] && tv[b].x > 0;
 #pragma unroll
-      for (int d = 0; d < 3; d++) {
-        cc[b][d] = 0.0;
-        sq[b][d] = 0;
-      }
-      if (xyzc) {
-        if (ok[b]) {
-          double p0[3], p1[3], p2[3], p3[3];
-          load_pt(xyzc, tv[b].x, p0);
-          load_pt(xyzc, tv[b].y, p1);
-          load_pt(xyzc, tv[b].z, p2);
-          load_pt(xyzc, tv[b].w, p3);
-#pragma unroll
-          for (int d = 0; d < 3; d++) cc[b][d] = 0.25 * ((p0[d] + p1[d]) + (p2[d] + p3[d]));
-        }
-        continue;
-      }
-      if (ok[b] && (v0only & 1)) { // measurement build (PMMG_HIP_SEEDV0=1): the first vertex stands for the centroid
-        const int *q0 = bg.xq + kXqStride * (size_t)(tv[b].x - 1);
-#pragma unroll
-        for (int d = 0; d < 3; d++) sq[b][d] = 4LL * q0[d];
-      } else if (ok[b]) {
+      for (int d = 0; d < 3; d++) sq[b][d] = 0;
+      if (ok[b]) {
         const int *q0 = bg.xq + kXqStride * (size_t)(tv[b].x - 1), *q1 = bg.xq + kXqStride * (size_t)(tv[b].y - 1);
         const int *q2 = bg.xq + kXqStride * (size_t)(tv[b].z - 1), *q3 = bg.xq + kXqStride * (size_t)(tv[b].w - 1);
         int a0[3], a1[3], a2[3], a3[3];
@@ -555,9 +519,9 @@ __global__ __launch_bounds__(kBlock) void k_seed_vol(Bg bg, Frame *fr, unsigned 
         float d2 = 0.f;
 #pragma unroll
         for (int d = 0; d < 3; d++) {
-          double t = xyzc ? (cc[b][d] - fr->lo[d]) * fr->inv_vol[d] : sa[d] + sb[d] * (double)sq[b][d];
+          double t = sa[d] + sb[d] * (double)sq[b][d];
           if ((adaptive >> d) & 1)
-            t = seed_pos(fr, d, xyzc ? cc[b][d] : fr->qc[d] + 0.25 * (double)sq[b][d] / fr->qs, g);
+            t = seed_pos(fr, d, fr->qc[d] + 0.25 * (double)sq[b][d] / fr->qs, g);
           c[d] = seed_cell(t, g);
           float f = (float)(t - c[d]);
           f = f < 0.f ? 0.f : (f > 0.999f ? 0.999f : f);
@@ -582,10 +546,7 @@ __global__ __launch_bounds__(kBlock) void k_seed_vol(Bg bg, Frame *fr, unsigned 
           if (o < r) leader = false;
         }
       }
-      if (leader) {
-        if (v0only & 2) cell[ci] = best; // measurement build (PMMG_HIP_SEEDNOATOM=1): the atomics' price
-        else atomicMin(&cell[ci], best);
-      }
+      if (leader) atomicMin(&cell[ci], best);
     }
   }
   for (int o = 32; o > 0; o >>= 1) {
@@ -1051,9 +1012,10 @@ __device__ __noinline__ void coherence_final(const Frame *fr, const double *cohd
 // earlier per-query atomicAdd on 2M bins took 1.9 ms at cfg4 on a shuffled
 // numbering; a hand-written two-level counting sort without global atomics
 // still 2.5 ms, its scattered partial-line writes across XCDs dominating),
-// and k_bin_split cuts the sorted ids into the volume list (plus a copy of
-// the volume queries' coordinates in processing order, so that the walk loads
-// them coalesced) and the surface list.  The radix sort is stable: the order
+// and k_bin_split cuts the sorted ids into the volume list and the surface
+// list (r03: a copy of the volume queries' coordinates in processing order,
+// which the walk then loads coalesced, took -0.5 ms off the walk on a shuffled
+// numbering and +1 ms in the binning).  The radix sort is stable: the order
 // is a deterministic function of the input.
 
 // flag: the order decision {sorted, bits per axis} (coherence_final); the kernel
@@ -1129,25 +1091,14 @@ __global__ __launch_bounds__(kBlock) void k_bin_keys(const double *xyz, const ui
   }
 }
 
-// sorted ids -> volume list (order_v, in place) + the volume queries'
-// coordinates in that order (qs, when non-null), surface list (order_b)
-__global__ __launch_bounds__(kBlock) void k_bin_split(const int *sorted_ids, const double *xyz, int np, int *order_b,
-                                                      double *qs, const DevStats *st, const int *flag) {
+// sorted ids -> volume list (order_v, in place), surface list (order_b)
+__global__ __launch_bounds__(kBlock) void k_bin_split(const int *sorted_ids, int *order_b, const DevStats *st,
+                                                      const int *flag) {
   if (flag[0] != 1) return;
   const int nvol = st->nvol, nbdy = st->nbdy;
-  for (long long j = (qs ? 0 : nvol) + blockIdx.x * (long long)blockDim.x + threadIdx.x; j < nvol + nbdy;
-       j += (long long)gridDim.x * blockDim.x) {
-    const int ip = sorted_ids[j];
-    if (j < nvol) {
-      if (qs) {
-        qs[3 * j] = xyz[3 * (size_t)(ip - 1)];
-        qs[3 * j + 1] = xyz[3 * (size_t)(ip - 1) + 1];
-        qs[3 * j + 2] = xyz[3 * (size_t)(ip - 1) + 2];
-      }
-    } else {
-      order_b[j - nvol] = ip;
-    }
-  }
+  for (long long j = nvol + blockIdx.x * (long long)blockDim.x + threadIdx.x; j < nvol + nbdy;
+       j += (long long)gridDim.x * blockDim.x)
+    order_b[j - nvol] = sorted_ids[j];
 }
 
 // Stable class compaction (the surface list, input-order path only): out =
@@ -1198,7 +1149,7 @@ __global__ __launch_bounds__(kBlock) void k_cls_scatter(const uint8_t *pclass, l
 }
 
 // ---------------------------------------------------------------- exhaustive-search helpers
-// (pmmg_fallback.hpp; the grids are built by the last blocks of k_vol_walk_exact and k_bdy)
+// (pmmg_fallback.hpp; the grids are built by k_fb_grid, after k_vol and k_bdy)
 
 // the last block of a grid to pass this point (after its device-scope
 // atomics) gets true: the other blocks' results are then visible to it.  The
@@ -1268,7 +1219,7 @@ __device__ __forceinline__ Box elem_box(const double (*p)[3], double extra, bool
 // grid cells its inflated box covers (r05: against every query of the list,
 // the scan cost ne x nfb box tests — 92 ms for 2644 queries over 120M tetra
 // in a carried iteration).  The grid is built by the last block of the kernel
-// that finishes the list (k_vol_walk_exact, k_bdy): G^3 cells over the
+// that finishes the list (k_vol, k_bdy): G^3 cells over the
 // queries' box, G = cbrt(nfb / 4) + 1 <= kFbGridMax; cells[c] .. cells[c + 1]
 // index items[], the list positions of cell c's queries.  A query inside an
 // element's box is in a cell of the box's (clamped) cell range, so the pairs

@@ -5,9 +5,9 @@
 //   k_vol             per query: fp32 filter walk from a grid seed to a
 //                     candidate tetra, the reference's exact fp64 acceptance
 //                     test there (and its exact coordinates), interpolation
-//                     of the metric and fields
-//   k_vol_walk_exact  the few queries the filter could not settle, walked and
-//                     interpolated in the reference's fp64 arithmetic (then
+//                     of the metric and fields; the few queries the filter
+//                     could not settle walk on in the reference's fp64
+//                     arithmetic (walk_exact) inside the same kernel (then
 //                     the exhaustive kernels, pmmg_fallback.hpp)
 #pragma once
 
@@ -22,23 +22,6 @@ __device__ __forceinline__ void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(0)
 struct VolLoc {
   int4 v;
   double phi[4];
-};
-
-struct ContEntry {
-  int ip; // query
-  int k;  // tetra the exact walk starts from (0: no seed)
-};
-
-// Located records of the split volume stage (r06): the walk kernel writes, per
-// processing index i, the accepted tetra's vertex ids (v.x = 0: nothing to
-// interpolate — another class, a handed-over or failed walk) and its four
-// exact coordinates; k_vol_interp reads them back in the same order.  Three
-// arrays of 16-byte rows, so that each wave-instruction writes or reads 1 KiB
-// of consecutive bytes.  Null v: the fused kernel interpolates itself.
-typedef int nti4 __attribute__((ext_vector_type(4)));
-struct LocBuf {
-  nti4 *v;
-  ntd2 *p01, *p23;
 };
 
 __device__ __forceinline__ void load_tet_pts(const Bg &bg, const int4 &tv, double (*p)[3]) {
@@ -206,7 +189,7 @@ __device__ __forceinline__ unsigned next_slots_packed(unsigned m, const int4 &tv
 // coordinate, ~1e-6 at most for the meshes at hand, is far below the
 // margin).  The exact test then runs once per query, at the candidate; a
 // query it rejects (within the margin of a face, ~1e-3 of the queries)
-// continues in exact arithmetic (k_vol_walk_exact).  Every located
+// continues in exact arithmetic (walk_exact).  Every located
 // tetra is therefore accepted by the reference's own test, with its exact
 // coordinates.
 //
@@ -359,7 +342,7 @@ struct LaneSlotsD {
 // (cfgG: 1 point in 3.9M otherwise).  The neighbour across the face of the
 // smallest coordinate is checked with the reference's own arithmetic.
 // (inlined: as an out-of-line call its pointer arguments kept the caller's
-// locals in scratch memory, 208 B per lane of k_vol_walk_exact in r03)
+// locals in scratch memory, 208 B per lane of the exact walk in r03)
 __device__ __forceinline__ void prefer_strict(const Bg &bg, const double *x, const int4 &ad, int &k, VolLoc *loc) {
   if (min4(loc->phi) > kEps) return;
   int f = 0; // the first smallest coordinate (compile-time indices only: phi stays in registers)
@@ -425,55 +408,6 @@ __device__ __forceinline__ int walk_exact(const Bg &bg, const double *x, int ip,
     L.put(sf, pn);
     tv = tn;
   }
-}
-
-// the queries the filter walk handed over, walked in exact arithmetic from
-// where it stopped (fresh visited history) and interpolated here (per-lane
-// gathers: these are few); failures -> the exhaustive list.  Fixed grid: the
-// count is read on the device.
-__global__ __launch_bounds__(64) void k_vol_walk_exact(Bg bg, const double *qxyz, int *fb, const ContEntry *cont,
-                                                       DevStats *st, Slots S, int *elem_out, int8_t *hit_out,
-                                                       int maxstep, FbInit fi, FbGridBufs gb) {
-  __shared__ BlockStats bs;
-  __shared__ double slot_img[12 * 64];
-  const LaneSlotsD L{&slot_img[__lane_id()]};
-  bstats_init(&bs);
-  __syncthreads();
-  const XcdChunk ch = xcd_chunk(st->ncont);
-  for (int it = 0; it < ch.iters; it++) {
-    const long long j = ch.start + it * ch.stride;
-    const bool active = j < ch.hi;
-    int status = 0, steps = 0, ip = 0;
-    if (active) {
-      const ContEntry e = cont[j];
-      ip = e.ip;
-      int k = e.k;
-      if (k > 0) {
-        double x[3];
-        load_pt(qxyz, ip, x);
-        VolLoc loc;
-        status = walk_exact(bg, x, ip, k, steps, maxstep, &loc, L);
-        if (status == 1) {
-          const int v[4] = {loc.v.x, loc.v.y, loc.v.z, loc.v.w};
-          for (int sl = 0; sl < S.n; sl++) interp_dyn<4>(S.s[sl], ip, v, loc.phi);
-          if (elem_out) elem_out[ip - 1] = k;
-          if (hit_out) hit_out[ip - 1] = (int8_t)PMMG_HIT_VOL_WALK;
-        }
-      }
-    }
-    const bool fail = active && status != 1;
-    const int slot = wave_append(&st->nfb_vol, fail);
-    if (fail) {
-      fb[slot] = ip;
-      fi.at(slot);
-    }
-    wave_count(&bs, kCntStuck, fail && status == 2);
-    wave_count(&bs, kCntLimit, fail && status == 3);
-    wave_stats(&bs, active, status == 1 ? PMMG_HIT_VOL_WALK : 0, steps);
-  }
-  __syncthreads();
-  bstats_flush(&bs, st);
-  // (the volume fallback list's query grid: k_fb_grid, launched next)
 }
 
 // ---------------------------------------------------------------- interpolation
@@ -575,7 +509,7 @@ __device__ __forceinline__ void sink_rows(const Slot &sl, const double *r, bool 
 //   2. the reference's exact test at the candidate (its 4 vertex rows are
 //      still in L1/L2 from the walk's last step), which gives the exact
 //      coordinates; rejected candidates, stuck and over-long walks go to the
-//      continuation list (k_vol_walk_exact);
+//      exact continuation (walk_exact, below);
 //   3. the interpolation of every slot (layout = template: codes 1 / 3 / 6,
 //      0 = none; C0 < 0 = runtime layout, per-lane).  A 3- or 6-double slot
 //      is gathered one vertex at a time: in pass i the 64 lanes load the 64
@@ -610,9 +544,8 @@ struct VolShared {
 };
 
 // The exact continuation inside k_vol (r06): a lane whose filter walk did not
-// end in an accepted tetra walks on in fp64 from where it stopped, as
-// k_vol_walk_exact does (same start, fresh history, same arithmetic: the
-// same tetra), and joins the wave's interpolation; only its failures go to
+// end in an accepted tetra walks on in fp64 from where it stopped (fresh
+// history), and joins the wave's interpolation; only its failures go to
 // the exhaustive list.  Before, the continuations (~0.07 % of the queries)
 // were a list and a kernel of their own after the volume kernel, 40-80 us on
 // the volume stage's tail beside the surface kernel's blocks.
@@ -620,7 +553,6 @@ struct ContArgs {
   int *fb;     // the volume fallback list (ids)
   FbInit fi;   // its best-index initialisation
   int maxstep; // the exact walk's step cap
-  int fuse;    // 1: continue in k_vol (0: the list + k_vol_walk_exact)
 };
 
 // Rows of one vertex of the wave's 64 queries, gathered cooperatively: piece
@@ -1011,8 +943,6 @@ __device__ __forceinline__ void vol_interp_wave(const Slots &S, bool acc, VolLoc
 }
 
 // PK: 0 = one array per solution, 1 / 2 = packed records in 1 / 2 passes.
-// lb.v non-null (split volume stage, r06; launched as the locate-only layout):
-// the located records go to lb and k_vol_interp interpolates them.
 // MAP = 1 (a call with a point map, pmmg_hip_set_point_map): a query whose
 // source vertex has a start tetra begins its filter walk there instead of at
 // the seed grid's tetra (PMMG_locate_setStart, the USE_POINTMAP branch of
@@ -1021,18 +951,14 @@ __device__ __forceinline__ void vol_interp_wave(const Slots &S, bool acc, VolLoc
 template <int PK, int C0, int C1, int C2, int C3, int C4, int C5, int MAP = 0>
 __global__ __launch_bounds__(64) void k_vol(Bg bg, const Frame *fr, const unsigned long long *grid, int g,
                                             const double *qxyz, const uint8_t *pclass, const int *order,
-                                            const double *qs, int np, ContEntry *cont, DevStats *st, Slots S,
-                                            int *elem_out, int8_t *hit_out, int filter_steps,
-                                            const int *order_flag, int xcd_run, int pad, int want, LocBuf lb,
-                                            int blk0, ContArgs ca, MapArgs ma) {
-  // want >= 0: the launch for one of the two orders (auto mode launches both, each after its own lists;
-  // the other returns at once)
-  if (want >= 0 && order_flag[0] != want) return;
+                                            int np, DevStats *st, Slots S, int *elem_out, int8_t *hit_out,
+                                            int filter_steps, const int *order_flag, int xcd_run, ContArgs ca,
+                                            MapArgs ma) {
   __shared__ VolShared<PK> sh;
   bstats_init(&sh.bs);
   __syncthreads();
   const LaneSlotsF L{(lds_float *)&sh.u.slots[__lane_id()]};
-  const int i = (blk0 + xcd_block_runs(xcd_run)) * 64 + threadIdx.x;
+  const int i = xcd_block_runs(xcd_run) * 64 + threadIdx.x;
   const bool sorted = order_flag[0] == 1; // the call's query order, decided on the device (the coherence test in k_bbox)
   bool active;
   int ip = 0;
@@ -1050,15 +976,13 @@ __global__ __launch_bounds__(64) void k_vol(Bg bg, const Frame *fr, const unsign
   bool noseed = false;
   [[maybe_unused]] bool mapped = false; // (MAP: the walk began from the point map)
   // the queries' coordinates, streamed once (non-temporal).  In input order
-  // (and in the binning's processing-order copy) the wave's 64 rows are one
-  // contiguous 1.5 KiB block: two instructions of 16-byte pieces through LDS
-  // touch its 24 sectors once, where three per-lane double loads touched
-  // them three times
+  // the wave's 64 rows are one contiguous 1.5 KiB block: two instructions of
+  // 16-byte pieces through LDS touch its 24 sectors once, where three
+  // per-lane double loads touched them three times (Morton order: per lane)
   {
-    const double *qrow = sorted ? qs : qxyz;
     const long long w0 = (long long)(i - __lane_id());
-    if (qrow && w0 + 64 <= (sorted ? (long long)st->nvol : (long long)np) && ((uintptr_t)qrow & 15) == 0) {
-      const ntd2 *src = reinterpret_cast<const ntd2 *>(qrow + 3 * w0);
+    if (!sorted && w0 + 64 <= (long long)np && ((uintptr_t)qxyz & 15) == 0) {
+      const ntd2 *src = reinterpret_cast<const ntd2 *>(qxyz + 3 * w0);
       ntd2 *dst = reinterpret_cast<ntd2 *>(sh.u.slots);
       const int lane = __lane_id();
       const ntd2 a = __builtin_nontemporal_load(src + lane);
@@ -1075,7 +999,7 @@ __global__ __launch_bounds__(64) void k_vol(Bg bg, const Frame *fr, const unsign
       wait_lgkm();
       __builtin_amdgcn_wave_barrier(); // the buffer holds the walk's vertex slots next
     } else if (active) {
-      load_pt_nt(sorted && qs ? qs : qxyz, sorted && qs ? i + 1 : ip, x);
+      load_pt_nt(qxyz, ip, x);
     }
   }
   if (active) {
@@ -1111,20 +1035,6 @@ __global__ __launch_bounds__(64) void k_vol(Bg bg, const Frame *fr, const unsign
           break;
         }
         ++steps;
-#ifdef PMMG_HIP_MEASURE
-        // measurement build, PMMG_HIP_PAD = v + 65536 t: v extra VALU
-        // instructions and t extra L1 accesses (re-loads of the current
-        // record) per walk step, to price each resource in the step
-        if (pad & 0x1FFFFFFF) {
-          float acc = (float)steps;
-          for (int j = 0; j < (pad & 0xFFFF); j++) asm volatile("v_add_f32 %0, %0, %0" : "+v"(acc));
-          int dummy = 0;
-          for (int j = 0; j < ((pad >> 16) & 0x1FFF); j++)
-            dummy += reinterpret_cast<const volatile int *>(bg.tetv + (size_t)(k - 1) * bg.tstride)[j & 3];
-          if (acc == -1.0f && dummy == 0x7FFFFFFF) steps += 0; // keep both chains alive
-          asm volatile("" ::"v"(acc), "v"(dummy));
-        }
-#endif
         const int r = step_f32(bg, xq, k, tv, ad, m, hist, L, walk_rsel(ip, steps));
         if (r != 0) {
           status = r;
@@ -1148,52 +1058,32 @@ __global__ __launch_bounds__(64) void k_vol(Bg bg, const Frame *fr, const unsign
     acc = exact_accept(x, p, tv, &loc, nullptr) && min4(loc.phi) > kEps;
   }
   const bool more = active && !acc;
-  if (ca.fuse && !lb.v) {
-    if (__any(more)) {
-      const LaneSlotsD LD{&sh.u.dslots[__lane_id()]};
-      __builtin_amdgcn_wave_barrier(); // the filter walk's slots are dead
-      int st2 = 0, steps2 = 0;
-      if (more && k > 0) {
-        st2 = walk_exact(bg, x, ip, k, steps2, ca.maxstep, &loc, LD);
-        acc = st2 == 1;
-      }
-      const bool fail = more && !acc;
-      const int fslot = wave_append(&st->nfb_vol, fail);
-      if (fail) {
-        ca.fb[fslot] = ip;
-        ca.fi.at(fslot);
-      }
-      wave_count(&sh.bs, kCntStuck, fail && st2 == 2);
-      wave_count(&sh.bs, kCntLimit, fail && st2 == 3);
-      steps += steps2;
-      __builtin_amdgcn_wave_barrier(); // (the interpolation's image aliases the fp64 slots)
+  if (__any(more)) { // the exact continuation (ContArgs)
+    const LaneSlotsD LD{&sh.u.dslots[__lane_id()]};
+    __builtin_amdgcn_wave_barrier(); // the filter walk's slots are dead
+    int st2 = 0, steps2 = 0;
+    if (more && k > 0) {
+      st2 = walk_exact(bg, x, ip, k, steps2, ca.maxstep, &loc, LD);
+      acc = st2 == 1;
     }
-  } else {
-    const int slot = wave_append(&st->ncont, more);
-    if (more) cont[slot] = ContEntry{ip, k};
+    const bool fail = more && !acc;
+    const int fslot = wave_append(&st->nfb_vol, fail);
+    if (fail) {
+      ca.fb[fslot] = ip;
+      ca.fi.at(fslot);
+    }
+    wave_count(&sh.bs, kCntStuck, fail && st2 == 2);
+    wave_count(&sh.bs, kCntLimit, fail && st2 == 3);
+    steps += steps2;
+    __builtin_amdgcn_wave_barrier(); // (the interpolation's image aliases the fp64 slots)
   }
   wave_stats(&sh.bs, active, acc ? PMMG_HIT_VOL_WALK : 0, steps);
   wave_count(&sh.bs, kCntVolQueries, active);
   wave_count(&sh.bs, kCntExact, more);
   wave_count(&sh.bs, kCntNoSeed, active && noseed);
   if constexpr (MAP != 0) wave_count(&sh.bs, kCntVolSrc, active && mapped);
-  if (lb.v && (sorted ? i < st->nvol : i < np)) { // split stage: the located record of processing index i
-    __builtin_nontemporal_store(acc ? nti4{loc.v.x, loc.v.y, loc.v.z, loc.v.w} : nti4{0, 0, 0, 0}, lb.v + i);
-    if (acc) {
-      __builtin_nontemporal_store(ntd2{loc.phi[0], loc.phi[1]}, lb.p01 + i);
-      __builtin_nontemporal_store(ntd2{loc.phi[2], loc.phi[3]}, lb.p23 + i);
-    }
-  }
   // 3. interpolation
-#ifdef PMMG_HIP_MEASURE
-  // measurement build: PMMG_HIP_PAD bit 30 — Morton order stores whole lines
-  // at the processing position (wrong rows, the scattered stores' price);
-  // bit 29 — no row stores in Morton order
-  const Sink snk{!sorted || ((pad >> 30) & 1), (size_t)(i - __lane_id()), ip};
-  if (sorted && ((pad >> 29) & 1)) acc = false;
-#else
   const Sink snk{!sorted, (size_t)(i - __lane_id()), ip};
-#endif
   if (__any(acc)) {
     if constexpr (PK > 0 || C0 != 0) vol_interp_wave<PK, C0, C1, C2, C3, C4, C5>(S, acc, loc, ip, sh.u.img, snk, sh.okm);
     if (acc) {
@@ -1208,50 +1098,6 @@ __global__ __launch_bounds__(64) void k_vol(Bg bg, const Frame *fr, const unsign
   }
   __syncthreads();
   bstats_flush(&sh.bs, st);
-}
-
-// ---------------------------------------------------------------- split interpolation (r06)
-//
-// The second kernel of the split volume stage: the located records of 64
-// consecutive processing indices per one-wave block (the walk kernel's block
-// order), read as whole lines, then the same wave-cooperative interpolation
-// as the fused kernel's third phase — but under its own register budget and
-// occupancy, where in the fused kernel the interpolation's gathers were issued
-// under the walk's.  Launched right after the walk kernel
-// on the same stream.
-template <int PK>
-struct InterpShared {
-  unsigned short okm[PK > 0 ? 64 : 1];
-  double img[(PK > 0 ? 16 : 8) * 64];
-};
-
-template <int PK, int C0, int C1, int C2, int C3, int C4, int C5>
-__global__ __launch_bounds__(64) void k_vol_interp(LocBuf lb, const int *order, const DevStats *st, int np, Slots S,
-                                                   const int *order_flag, int xcd_run, int want, int blk0) {
-  if (want >= 0 && order_flag[0] != want) return;
-  __shared__ InterpShared<PK> sh;
-  const int i = (blk0 + xcd_block_runs(xcd_run)) * 64 + threadIdx.x;
-  const bool sorted = order_flag[0] == 1;
-  const int bound = sorted ? st->nvol : np;
-  VolLoc loc;
-  bool acc = false;
-  int ip = 0;
-  if (i < bound) {
-    const nti4 v = __builtin_nontemporal_load(lb.v + i);
-    acc = v.x != 0;
-    loc.v = make_int4(v.x, v.y, v.z, v.w);
-    if (acc) {
-      const ntd2 a = __builtin_nontemporal_load(lb.p01 + i), b = __builtin_nontemporal_load(lb.p23 + i);
-      loc.phi[0] = a.x;
-      loc.phi[1] = a.y;
-      loc.phi[2] = b.x;
-      loc.phi[3] = b.y;
-    }
-    ip = sorted ? order[i] : i + 1;
-  }
-  if (!__any(acc)) return;
-  const Sink snk{!sorted, (size_t)(i - __lane_id()), ip};
-  vol_interp_wave<PK, C0, C1, C2, C3, C4, C5>(S, acc, loc, ip, sh.img, snk, sh.okm);
 }
 
 } // namespace pmmg

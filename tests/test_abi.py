@@ -109,3 +109,21 @@ def test_abi_version_and_stats_size():
     lib = _native.hip_lib()
     assert lib.pmmg_hip_abi_version() == v == _native.ABI_VERSION
     assert lib.pmmg_hip_stats_size() == ctypes.sizeof(_native.HipStats)
+
+
+def test_every_environment_name_read_is_documented():
+    """The names the libraries read from the environment (getenv, env_int,
+    env_int_any anywhere under parmmg_amd/csrc) are exactly the names the
+    'Environment' paragraph of INTEGRATION.md §4 documents: a switch added for
+    an experiment is documented or removed with the experiment."""
+    csrc = os.path.join(ROOT, "parmmg_amd", "csrc")
+    read = set()
+    for fn in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, fn)).read()
+        read |= set(re.findall(r'\b(?:getenv|env_int|env_int_any)\(\s*"(PMMG_(?:HIP|HOST)_[A-Z0-9_]+)"', text))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec = doc[doc.index("## 4. Options"):]
+    para = sec[sec.index("\nEnvironment, read at creation"):].split("\n\n")[0]
+    documented = set(re.findall(r"`(PMMG_(?:HIP|HOST)_[A-Z0-9_]+)(?:=\w+)?`", para))
+    assert len(read) >= 10
+    assert read == documented, (sorted(read - documented), sorted(documented - read))
