@@ -22,12 +22,12 @@
 // Rows have 0 to 4 entries, so a lane's own offset is data dependent: stored
 // from the lanes directly the entries would leave as scattered 4-byte words.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "pmmg_graph.hpp"
+#include "pmmg_devutil.hpp"
 #include "pmmg_quality.hpp"
 
 namespace {
@@ -224,55 +224,19 @@ __global__ __launch_bounds__(kGBlock) void k_graph_fill(const double *xyz, int n
   if (MODE != W_NONE) flush_run(s_wgt, adjwgt + base - ow, ow, ow + n);
 }
 
-template <class T>
-T *slot(GraphCache *c, int i, size_t count) {
-  const size_t bytes = count * sizeof(T) > 0 ? count * sizeof(T) : 16;
-  if (c->cap[i] < bytes) {
-    if (c->p[i]) (void)hipFree(c->p[i]);
-    c->p[i] = nullptr;
-    c->cap[i] = 0;
-    if (hipMalloc(&c->p[i], bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    c->cap[i] = bytes;
-  }
-  return static_cast<T *>(c->p[i]);
-}
-
-enum { S_BTOT, S_BOFF, S_SCAN, S_FLAGS, S_ADJA };
-
-#define GCK(expr)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) {                                                                         \
-      snprintf(msg, msglen, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return 0;                                                                                     \
-    }                                                                                               \
-  } while (0)
-
 } // namespace
-
-void pmmg_graph_cache_free(GraphCache *c) {
-  if (!c) return;
-  for (int i = 0; i < GraphCache::kSlots; i++) {
-    if (c->p[i]) (void)hipFree(c->p[i]);
-    c->p[i] = nullptr;
-    c->cap[i] = 0;
-  }
-}
 
 int pmmg_graph_metis(hipStream_t s, int np, const double *xyz, int ne, const int *tetv, int tstride, const int *adja,
                      int astride, int want_wgt, int met_size, const double *met, int cap, int64_t *nadjncy, int *xadj,
                      int *adjncy, int *adjwgt, GraphCache *cache, SnapCache *snap, char *msg, size_t msglen) {
   *nadjncy = 0;
   if (ne == 0) {
-    GCK(hipMemsetAsync(xadj, 0, sizeof(int), s));
-    GCK(hipStreamSynchronize(s));
+    DEVCK(hipMemsetAsync(xadj, 0, sizeof(int), s));
+    DEVCK(hipStreamSynchronize(s));
     return 1;
   }
   if (!adja) { // MMG3D_hashTetra's branch of src/metis_pmmg.c:756
-    int *built = slot<int>(cache, S_ADJA, 4 * (size_t)ne);
+    int *built = get<int>(cache->adja, 4 * (size_t)ne);
     if (!built) {
       snprintf(msg, msglen, "metis_graph: out of device memory (adjacency of %d tetra)", ne);
       return 0;
@@ -283,26 +247,25 @@ int pmmg_graph_metis(hipStream_t s, int np, const double *xyz, int ne, const int
   }
   const int4 *tv = reinterpret_cast<const int4 *>(tetv), *av = reinterpret_cast<const int4 *>(adja);
   const int nblk = (ne + kGBlock - 1) / kGBlock;
-  int *btot = slot<int>(cache, S_BTOT, (size_t)nblk + 1), *boff = slot<int>(cache, S_BOFF, (size_t)nblk + 1);
-  int *flags = slot<int>(cache, S_FLAGS, 4);
-  size_t tb = 0;
-  GCK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, btot, boff, nblk + 1, s));
-  void *tmp = slot<char>(cache, S_SCAN, tb);
-  if (!btot || !boff || !flags || !tmp) {
+  int *btot = get<int>(cache->btot, (size_t)nblk + 1), *boff = get<int>(cache->boff, (size_t)nblk + 1);
+  int *flags = get<int>(cache->flags, 4);
+  if (!btot || !boff || !flags) {
     snprintf(msg, msglen, "metis_graph: out of device memory (block counts)");
     return 0;
   }
+  size_t tb = 0; // (the scan's temporary is allocated here, ahead of the count kernel)
+  if (!scan_reserve(cache->scan, btot, boff, nblk + 1, s, &tb, msg, msglen)) return 0;
   // count, scan (one entry more than blocks: boff[nblk] is the total)
-  GCK(hipMemsetAsync(flags, 0, 4 * sizeof(int), s));
-  GCK(hipMemsetAsync(btot + nblk, 0, sizeof(int), s));
+  DEVCK(hipMemsetAsync(flags, 0, 4 * sizeof(int), s));
+  DEVCK(hipMemsetAsync(btot + nblk, 0, sizeof(int), s));
   hipLaunchKernelGGL(k_graph_count, dim3(nblk), dim3(kGBlock), 0, s, ne, tv, tstride, av, astride, want_wgt ? np : 0,
                      btot, flags);
-  GCK(hipGetLastError());
-  GCK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, btot, boff, nblk + 1, s));
+  DEVCK(hipGetLastError());
+  if (!exclusive_scan(cache->scan, btot, boff, nblk + 1, s, msg, msglen)) return 0;
   int h_flags = 0, h_total = 0;
-  GCK(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, s));
-  GCK(hipMemcpyAsync(&h_total, boff + nblk, sizeof(int), hipMemcpyDeviceToHost, s));
-  GCK(hipStreamSynchronize(s));
+  DEVCK(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, s));
+  DEVCK(hipMemcpyAsync(&h_total, boff + nblk, sizeof(int), hipMemcpyDeviceToHost, s));
+  DEVCK(hipStreamSynchronize(s));
   if (h_flags & G_BADLINK) {
     snprintf(msg, msglen, "metis_graph: an adja entry lies outside [4, 4*%d+3] (nothing written to the lists)", ne);
     return 0;
@@ -314,9 +277,9 @@ int pmmg_graph_metis(hipStream_t s, int np, const double *xyz, int ne, const int
   }
   if (h_flags & G_UNUSED) {
     hipLaunchKernelGGL(k_graph_links_used, dim3(nblk), dim3(kGBlock), 0, s, ne, tv, tstride, av, astride, flags);
-    GCK(hipGetLastError());
-    GCK(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, s));
-    GCK(hipStreamSynchronize(s));
+    DEVCK(hipGetLastError());
+    DEVCK(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, s));
+    DEVCK(hipStreamSynchronize(s));
     if (h_flags & G_TOUNUSED) {
       snprintf(msg, msglen, "metis_graph: an adja entry points to an unused tetra: the mesh must be packed (nothing "
                             "written to the lists)");
@@ -339,8 +302,8 @@ int pmmg_graph_metis(hipStream_t s, int np, const double *xyz, int ne, const int
     default: FILL(W_HUGE); break;
   }
 #undef FILL
-  GCK(hipGetLastError());
-  GCK(hipStreamSynchronize(s));
+  DEVCK(hipGetLastError());
+  DEVCK(hipStreamSynchronize(s));
   if (!lists) {
     snprintf(msg, msglen, "metis_graph: %d graph entries exceed cap = %d (nothing written to the lists)", h_total, cap);
     return 0;

@@ -9,15 +9,12 @@
 #include "pmmg_snapshot.hpp"
 
 // Device scratch of the graph passes, owned by a context and kept between
-// calls (grown, never shrunk): per-block counts and offsets, the scan's
-// temporary, the flags, and the adjacency of a call that came without one.
-// Freed by pmmg_graph_cache_free (pmmg_hip_release_scratch).
+// calls (grown, never shrunk).
 struct GraphCache {
-  static constexpr int kSlots = 5;
-  void *p[kSlots] = {};
-  size_t cap[kSlots] = {};
+  DevBuf btot, boff, scan; // per-block counts, their offsets, the scan's temporary
+  DevBuf flags;            // the call's flag bits
+  DevBuf adja;             // the adjacency of a call that came without one
 };
-void pmmg_graph_cache_free(GraphCache *c);
 
 // pmmg_hip_metis_graph on checked arguments.  Tetra rows are int4 rows
 // `tstride` / `astride` int4s apart (1: separate arrays, 2: tet8); tetv may be

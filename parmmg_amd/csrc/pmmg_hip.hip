@@ -132,9 +132,47 @@ bool packed_supported(int met_size, int nfield, const int *fsize) {
 
 // ================================================================ host side
 
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
+// Every device buffer a context owns, in one base of the context: each frees
+// itself (pmmg_devbuf.hpp), and pmmg_hip_destroy resets the whole base at the
+// point of its teardown where the streams are idle and still exist.
+struct CtxBufs {
+  // owned copies for PMMG_HIP_HOST inputs
+  DevBuf o_xyz, o_tetv, o_adja, o_triv, o_adjt, o_met, o_rec;
+  std::vector<DevBuf> o_f;
+  DevBuf o_tet4; // device copy of a host tetv (input of the device adjacency)
+  // work buffers
+  DevBuf frame, stats, grid, sgrid, order_v, order_b, xq;
+  DevBuf cohd;                            // the coherence test's sampled distances (k_bbox)
+  DevBuf axh;                             // per-axis histograms of the seed grid map (k_quantize)
+  DevBuf bkeys, bkeys2, bvals, bvals2;    // Morton binning: keys and ids, ping-ponged by the radix sort
+  DevBuf rs_hist, rs_csum;                // the radix sort's digit table and its scan's chunk sums
+  DevBuf cls_cnt;                         // per-block class counts (surface list compaction)
+  DevBuf oflag;                           // the coherence test's {sorted, bin_bits} on the device
+  DevBuf qmin;                               // tetra quality minimum (pmmg_hip_tetra_qual)
+  DevBuf fb_vol, fb_bdy, best, nac, cres, bbest, bnac, bcres; // exhaustive searches: fallback lists, lowest
+  DevBuf fbp_vol, fbp_bdy; // accepting element, unaccepted lists, closest results and range minima (FbPart)
+  DevBuf fbg_vol_c, fbg_vol_u, fbg_vol_i, fbg_bdy_c, fbg_bdy_u, fbg_bdy_i; // the lists' query grids
+  // host-mode staging
+  DevBuf h_xyz, h_cls, h_met, h_elem, h_hit;
+  std::vector<DevBuf> h_f;
+  SnapCache snap_cache; // the snapshot kernels' scratch (pmmg_snapshot.hip)
+  StatsCache stats_cache; // pmmg_hip_qual_histo / pmmg_hip_edge_lengths: edge table, slabs (pmmg_meshstats.hip)
+  GraphCache graph_cache; // pmmg_hip_metis_graph: block counts, scan scratch, a built adjacency (pmmg_graph.hip)
+  // carry-over (pmmg_hip_keep / pmmg_hip_carry_over): kept[slot] holds the new
+  // points and written rows of a host-mode call
+  struct Kept {
+    DevBuf xyz, met;
+    std::vector<DevBuf> f;
+    int np = 0, met_size = 0;
+    std::vector<int> fsize;
+    bool valid = false;
+  };
+  std::vector<Kept> kept;
+  DevBuf carry_dsrc, carry_need, carry_ids, carry_cnt, carry_rows, carry_bc;
+  DevBuf map_own;  // the copy of a PMMG_HIP_HOST map
+  DevBuf map_need; // the call's volume / surface queries without a mapped start (k_map_count)
+  DevBuf start_tab; // the background's start tables (see pmmg_hip_ctx::map_src)
+  DevBuf ag_send, ag_recv, ag_off, ag_chk; // the all-gather's buffers (ag_chk: its agreement, ag_agree)
 };
 
 enum {
@@ -142,7 +180,7 @@ enum {
   EV_SB0, EV_ORDER2, EV_FILL, EV_COUNT
 };
 
-struct pmmg_hip_ctx {
+struct pmmg_hip_ctx : CtxBufs {
   int device = 0;
   int options = 0;
   hipStream_t stream = nullptr;
@@ -161,28 +199,10 @@ struct pmmg_hip_ctx {
   const double *met = nullptr;
   const double *rec = nullptr; // packed per-vertex solution records (set_solutions_packed), else null
   int rstride = 0;             // their stride in doubles
-  // owned copies for PMMG_HIP_HOST inputs
-  DevBuf o_xyz, o_tetv, o_adja, o_triv, o_adjt, o_met, o_rec;
-  std::vector<DevBuf> o_f;
-  // work buffers
-  DevBuf frame, stats, grid, sgrid, order_v, order_b, xq;
-  DevBuf cohd;                            // the coherence test's sampled distances (k_bbox)
-  DevBuf axh;                             // per-axis histograms of the seed grid map (k_quantize)
-  DevBuf bkeys, bkeys2, bvals, bvals2;    // Morton binning: keys and ids, ping-ponged by the radix sort
-  DevBuf rs_hist, rs_csum;                // the radix sort's digit table and its scan's chunk sums
   // the seed grids left clean by the previous call (its last kernels refill
   // them while the other stream finishes): k_reset skips what is clean
   void *grid_clean_p = nullptr, *sgrid_clean_p = nullptr;
   long long grid_clean_n = 0, sgrid_clean_n = 0;
-  DevBuf cls_cnt;                         // per-block class counts (surface list compaction)
-  DevBuf oflag;                           // the coherence test's {sorted, bin_bits} on the device
-  DevBuf qmin;                               // tetra quality minimum (pmmg_hip_tetra_qual)
-  DevBuf fb_vol, fb_bdy, best, nac, cres, bbest, bnac, bcres; // exhaustive searches: fallback lists, lowest
-  DevBuf fbp_vol, fbp_bdy; // accepting element, unaccepted lists, closest results and range minima (FbPart)
-  DevBuf fbg_vol_c, fbg_vol_u, fbg_vol_i, fbg_bdy_c, fbg_bdy_u, fbg_bdy_i; // the lists' query grids
-  // host-mode staging
-  DevBuf h_xyz, h_cls, h_met, h_elem, h_hit;
-  std::vector<DevBuf> h_f;
   hipEvent_t ev[EV_COUNT] = {};
   bool pending = false;
   // host-mode transfers: two pinned staging buffers, filled / drained by a
@@ -192,10 +212,6 @@ struct pmmg_hip_ctx {
   hipEvent_t stage_ev[2] = {};
   int stage_i = 0;
   struct Pool *pool = nullptr;
-  DevBuf o_tet4; // device copy of a host tetv (input of the device adjacency)
-  SnapCache snap_cache; // the snapshot kernels' scratch (pmmg_snapshot.hip)
-  StatsCache stats_cache; // pmmg_hip_qual_histo / pmmg_hip_edge_lengths: edge table, slabs (pmmg_meshstats.hip)
-  GraphCache graph_cache; // pmmg_hip_metis_graph: block counts, scan scratch, a built adjacency (pmmg_graph.hip)
   int edge_hash = 1;      // the edge table's slot: 1 a run of slots per low vertex first, 0 a mix of the whole
                           // key (PMMG_HIP_EDGEHASH=0; cfg4: 31.0 against 56.0 ms)
   // host mode: the device-built background (adjacency, boundary trias) runs
@@ -225,20 +241,11 @@ struct pmmg_hip_ctx {
   // carry-over (pmmg_hip_keep / pmmg_hip_carry_over): kept[slot] holds the new
   // points and written rows of a host-mode call; an armed carry (carry_slot
   // >= 0) feeds the next host-mode set_background / set_solutions from it
-  struct Kept {
-    DevBuf xyz, met;
-    std::vector<DevBuf> f;
-    int np = 0, met_size = 0;
-    std::vector<int> fsize;
-    bool valid = false;
-  };
-  std::vector<Kept> kept;
   int last_host_np = 0, last_host_met = 0; // the last host-mode locate_interp (what pmmg_hip_keep keeps)
   std::vector<int> last_host_fsize;
   int carry_slot = -1, carry_np = 0;
   bool carry_bg = false;       // set_background took its vertices from the carry
   std::vector<int> carry_src;  // next vertex i+1 = kept point carry_src[i] (0: host row); empty: identity
-  DevBuf carry_dsrc, carry_need, carry_ids, carry_cnt, carry_rows, carry_bc;
   int64_t bytes_up = 0; // host -> device bytes of host-mode calls (pmmg_hip_bytes_up)
   // point map (pmmg_hip_set_point_map): map_src != null arms the next locate_interp(_rec) of map_np new
   // points, which consumes it.  start_tab: the background's start tables, start_tet[np] then start_tri[np]
@@ -246,9 +253,6 @@ struct pmmg_hip_ctx {
   // and kept until the next set_background* or pmmg_hip_release_scratch
   const int *map_src = nullptr;
   int map_np = 0;
-  DevBuf map_own;  // the copy of a PMMG_HIP_HOST map
-  DevBuf map_need; // the call's volume / surface queries without a mapped start (k_map_count)
-  DevBuf start_tab;
   bool start_valid = false;
   // pmmg_hip_locate_interp_groups: lanes[j] is lane j (same device and
   // options, created at the first groups call); lane 0 enqueues on this
@@ -262,7 +266,6 @@ struct pmmg_hip_ctx {
   ncclComm_t comm = nullptr;
   bool comm_owned = false;
   int comm_rank = 0, comm_size = 0;
-  DevBuf ag_send, ag_recv, ag_off, ag_chk; // (ag_chk: the all-gather's agreement, ag_agree)
   // PMMG_HIP_GROUP_LANES: most lanes of a groups call (r05k, 10 cfg2-size groups, 4 hardware queues: 4 / 5 /
   // 8 / 10 lanes 0.096 / 0.083 / 0.092 / 0.095 ms per group — 5 lanes take 2 groups each, 4 take 3, 3, 2, 2;
   // more hardware queues made it slower: 8 queues, 5 lanes 0.127; r04i: 1 / 2 lanes 0.165 / 0.125)
@@ -311,15 +314,11 @@ static hipError_t ctx_d2h(pmmg_hip_ctx *c, void *dst, const void *src, size_t n)
 }
 
 static int ensure(pmmg_hip_ctx *c, DevBuf &b, size_t bytes) {
-  if (bytes == 0) bytes = 16;
-  if (b.cap >= bytes) return 1;
-  if (b.p) {
-    HIPCK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
+  const hipError_t e = b.ensure(bytes);
+  if (e != hipSuccess) {
+    set_err(c, "hipMalloc(&b.p, bytes) failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+    return 0;
   }
-  HIPCK(c, hipMalloc(&b.p, bytes));
-  b.cap = bytes;
   return 1;
 }
 
@@ -330,12 +329,6 @@ static int ensure(pmmg_hip_ctx *c, DevBuf &b, size_t bytes) {
 static int copy_stream(pmmg_hip_ctx *c) {
   if (!c->cstream) HIPCK(c, hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
   return 1;
-}
-
-static void release(DevBuf &b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
 }
 
 // ---------------------------------------------------------------- host-mode transfers
@@ -570,6 +563,15 @@ static int snap_join(pmmg_hip_ctx *c) {
   return 1;
 }
 
+// what opens an entry point that works on the device: the context's device
+// made current, then a deferred snapshot joined
+static int enter(pmmg_hip_ctx *c) {
+  if (!c) return 0;
+  HIPCK(c, hipSetDevice(c->device));
+  if (!snap_join(c)) return 0;
+  return 1;
+}
+
 // 16-byte streaming stores (a from hipMalloc: 16-byte aligned); the odd last
 // element by the first thread.  (r05: 8-byte stores refilled cfg4's 101 MB
 // seed grid in 43 us, ~2.3 TB/s)
@@ -673,15 +675,8 @@ void pmmg_hip_destroy(pmmg_hip_ctx *c) {
   if (c->stream3) (void)hipStreamSynchronize(c->stream3);
   if (c->stream_f) (void)hipStreamSynchronize(c->stream_f);
   if (c->cstream) (void)hipStreamSynchronize(c->cstream);
-  DevBuf *bufs[] = {&c->o_xyz, &c->o_tetv, &c->o_adja, &c->o_triv, &c->o_adjt, &c->o_met, &c->o_rec, &c->frame,
-                    &c->stats, &c->grid, &c->sgrid, &c->order_v, &c->cohd,
-                    &c->order_b, &c->xq, &c->axh, &c->bkeys, &c->bkeys2, &c->bvals, &c->bvals2, &c->rs_hist, &c->rs_csum, &c->oflag, &c->cls_cnt, &c->qmin, &c->fb_vol, &c->fb_bdy,
-                    &c->best, &c->nac, &c->cres, &c->bbest, &c->bnac, &c->bcres, &c->fbp_vol, &c->fbp_bdy, &c->fbg_vol_c,
-                    &c->fbg_vol_u, &c->fbg_vol_i, &c->fbg_bdy_c, &c->fbg_bdy_u, &c->fbg_bdy_i, &c->h_xyz,
-                    &c->h_cls, &c->h_met, &c->h_elem, &c->h_hit, &c->map_own, &c->map_need, &c->start_tab};
-  for (DevBuf *b : bufs) release(*b);
-  for (auto &b : c->o_f) release(b);
-  for (auto &b : c->h_f) release(b);
+  // every stream is idle and still exists: the device buffers go now, before the streams
+  *static_cast<CtxBufs *>(c) = CtxBufs{};
   for (int i = 0; i < EV_COUNT; i++)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
   for (int b = 0; b < 2; b++) {
@@ -689,18 +684,6 @@ void pmmg_hip_destroy(pmmg_hip_ctx *c) {
     if (c->stage_ev[b]) (void)hipEventDestroy(c->stage_ev[b]);
   }
   delete c->pool;
-  release(c->o_tet4);
-  pmmg_snap_cache_free(&c->snap_cache);
-  pmmg_stats_cache_free(&c->stats_cache);
-  pmmg_graph_cache_free(&c->graph_cache);
-  for (auto &k : c->kept) {
-    release(k.xyz);
-    release(k.met);
-    for (auto &b : k.f) release(b);
-  }
-  DevBuf *cb[] = {&c->carry_dsrc, &c->carry_need, &c->carry_ids, &c->carry_cnt, &c->carry_rows, &c->carry_bc,
-                  &c->ag_send, &c->ag_recv, &c->ag_off, &c->ag_chk};
-  for (DevBuf *b : cb) release(*b);
   if (c->comm && c->comm_owned && rccl().ok) (void)rccl().commDestroy(c->comm);
   if (!c->borrowed_streams) {
     if (c->stream2 && c->stream2 != c->stream) (void)hipStreamDestroy(c->stream2);
@@ -912,9 +895,7 @@ static int carry_solutions_body(pmmg_hip_ctx *c, int met_size, const double *met
 // triv given: the tria adjacency is built on the device.
 static int set_background_impl(pmmg_hip_ctx *c, int np, const double *xyz, int ne, const int *tetv, const int *adja,
                                const int *tet8, int nt, const int *triv, const int *adjt, double hausd, int where) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   c->start_valid = false; // (the start tables belong to the background they were built on)
   const bool packed = tet8 != nullptr;
   const bool build_bdy = nt < 0 && !triv;
@@ -1757,9 +1738,7 @@ static int collect_stats(pmmg_hip_ctx *c, pmmg_hip_stats *out) {
 }
 
 int pmmg_hip_sync(pmmg_hip_ctx *c, pmmg_hip_stats *stats) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   for (pmmg_hip_ctx *l : c->lanes)
     if (hipStreamSynchronize(l->stream) != hipSuccess) {
       set_err(c, "sync: group lane failed: %s", l->err);
@@ -1802,9 +1781,7 @@ int pmmg_hip_set_point_map(pmmg_hip_ctx *c, int np_new, const int *src, int wher
 }
 
 int pmmg_hip_start_elements(pmmg_hip_ctx *c, int *start_tet, int *start_tri, int where) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   if (c->bg.ne <= 0) {
     set_err(c, "start_elements: no background set");
     return 0;
@@ -1985,11 +1962,7 @@ int pmmg_hip_carry_over(pmmg_hip_ctx *c, int slot, int np, const int *src) {
       HIPCK(c, hipSetDevice(c->device));
       if (!snap_join(c)) return 0;
       HIPCK(c, hipStreamSynchronize(c->stream));
-      release(k.xyz);
-      release(k.met);
-      for (auto &b : k.f) release(b);
-      k.f.clear();
-      k.valid = false;
+      k = pmmg_hip_ctx::Kept{};
     }
     if (c->carry_slot == slot) carry_disarm(c);
     return 1;
@@ -2019,16 +1992,14 @@ int pmmg_hip_carry_over(pmmg_hip_ctx *c, int slot, int np, const int *src) {
 }
 
 int pmmg_hip_release_scratch(pmmg_hip_ctx *c) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   HIPCK(c, hipStreamSynchronize(c->stream));
   HIPCK(c, hipStreamSynchronize(c->stream2));
   if (c->stream3) HIPCK(c, hipStreamSynchronize(c->stream3));
-  pmmg_snap_cache_free(&c->snap_cache);
-  pmmg_stats_cache_free(&c->stats_cache);
-  pmmg_graph_cache_free(&c->graph_cache);
-  for (DevBuf *b : {&c->bvals2, &c->rs_hist, &c->rs_csum, &c->start_tab}) release(*b);
+  c->snap_cache = SnapCache{};
+  c->stats_cache = StatsCache{};
+  c->graph_cache = GraphCache{};
+  for (DevBuf *b : {&c->bvals2, &c->rs_hist, &c->rs_csum, &c->start_tab}) b->release();
   c->start_valid = false; // (the next call with a point map builds the start tables again)
   for (pmmg_hip_ctx *l : c->lanes) pmmg_hip_destroy(l);
   c->lanes.clear();
@@ -2167,9 +2138,7 @@ int pmmg_hip_locate_interp_groups(pmmg_hip_ctx *c, int ngroup, const pmmg_hip_gr
 static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 int pmmg_hip_build_adjacency(pmmg_hip_ctx *c, int np, int ne, const int *tetv, int *adja, int *tet8) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   if (np <= 0 || ne <= 0 || !tetv || (!adja && !tet8)) {
     set_err(c, "build_adjacency: invalid arguments (np=%d ne=%d)", np, ne);
     return 0;
@@ -2187,9 +2156,7 @@ int pmmg_hip_build_adjacency(pmmg_hip_ctx *c, int np, int ne, const int *tetv, i
 
 int pmmg_hip_tetra_qual(pmmg_hip_ctx *c, int np, const double *xyz, int ne, const int *tetv, int met_size,
                         const double *met, double *qual, double *minqual) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   if (np < 0 || ne < 0 || (ne > 0 && (!xyz || !tetv || !qual)) || !minqual ||
       (met_size == 6 && ne > 0 && !met) || (met_size != 0 && met_size != 1 && met_size != 6)) {
     set_err(c, "tetra_qual: invalid arguments (np=%d ne=%d met_size=%d)", np, ne, met_size);
@@ -2218,9 +2185,7 @@ int pmmg_hip_tetra_qual(pmmg_hip_ctx *c, int np, const double *xyz, int ne, cons
 }
 
 int pmmg_hip_qual_histo(pmmg_hip_ctx *c, int ne, const int *tetv, const double *qual, pmmg_hip_qual_histo_t *out) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   if (ne < 0 || (ne > 0 && (!tetv || !qual)) || !out) {
     set_err(c, "qual_histo: invalid arguments (ne=%d)", ne);
     return 0;
@@ -2235,9 +2200,7 @@ int pmmg_hip_qual_histo(pmmg_hip_ctx *c, int ne, const int *tetv, const double *
 int pmmg_hip_edge_lengths(pmmg_hip_ctx *c, int np, const double *xyz, int ne, const int *tetv, int met_size,
                           const double *met, int nskip, const int *skip, pmmg_hip_len_histo_t *out, int cap,
                           int *edge_out, double *len_out) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   if (met_size != 1 && met_size != 6) {
     set_err(c, "edge_lengths: met_size %d (an edge length needs an iso (1) or aniso (6) metric)", met_size);
     return 0;
@@ -2259,9 +2222,7 @@ int64_t pmmg_hip_mesh_stats_bytes(pmmg_hip_ctx *c) { return c ? pmmg_stats_cache
 
 int pmmg_hip_compute_wgt_mesh(pmmg_hip_ctx *c, int np, const double *xyz, int ne, const int *tetv, const int *xt,
                               const uint16_t *ftag, int met_size, const double *met, int tag, double *qual) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   if (np < 0 || ne < 0 || (ne > 0 && (!xyz || !tetv || !xt || !ftag || !qual)) ||
       (met_size != 0 && met_size != 1 && met_size != 6) || (met_size && ne > 0 && !met)) {
     set_err(c, "compute_wgt_mesh: invalid arguments (np=%d ne=%d met_size=%d)", np, ne, met_size);
@@ -2280,9 +2241,7 @@ int pmmg_hip_compute_wgt_mesh(pmmg_hip_ctx *c, int np, const double *xyz, int ne
 
 int pmmg_hip_compute_wgt_faces(pmmg_hip_ctx *c, int np, const double *xyz, const int *tetv, int nface,
                                const int *face, int met_size, const double *met, double *wgt) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   if (np < 0 || nface < 0 || (nface > 0 && (!xyz || !tetv || !face || !wgt)) ||
       (met_size != 0 && met_size != 1 && met_size != 6) || (met_size && nface > 0 && !met)) {
     set_err(c, "compute_wgt_faces: invalid arguments (np=%d nface=%d met_size=%d)", np, nface, met_size);
@@ -2302,9 +2261,7 @@ int pmmg_hip_compute_wgt_faces(pmmg_hip_ctx *c, int np, const double *xyz, const
 int pmmg_hip_metis_graph(pmmg_hip_ctx *c, int np, const double *xyz, int ne, const int *tetv, const int *adja,
                          const int *tet8, int met_size, const double *met, int cap, int64_t *nadjncy, int *xadj,
                          int *adjncy, int *adjwgt) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   const bool packed = tet8 != nullptr, wgt = adjwgt != nullptr;
   if (np < 0 || ne < 0 || !nadjncy || !xadj || cap < 0 || (cap > 0 && !adjncy) ||
       (ne > 0 && !packed && !tetv && (!adja || wgt)) ||
@@ -2335,9 +2292,7 @@ int pmmg_hip_metis_graph(pmmg_hip_ctx *c, int np, const double *xyz, int ne, con
 
 int pmmg_hip_build_boundary(pmmg_hip_ctx *c, int np, int ne, const int *tet8, const int *tetv, const int *adja,
                             const int *tref, int cap, int *nt, int *triv, int *adjt) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   const bool packed = tet8 != nullptr;
   if (np <= 0 || ne <= 0 || !nt || (!packed && (!tetv || !adja)) || cap < 0 || (cap > 0 && !triv)) {
     set_err(c, "build_boundary: invalid arguments (np=%d ne=%d cap=%d)", np, ne, cap);
@@ -2364,9 +2319,7 @@ void *pmmg_hip_malloc(pmmg_hip_ctx *c, int64_t bytes) {
 }
 
 int pmmg_hip_free(pmmg_hip_ctx *c, void *p) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   HIPCK(c, hipFree(p));
   return 1;
 }
@@ -2409,9 +2362,7 @@ static void comm_release(pmmg_hip_ctx *c) {
 static constexpr int kAgView = 8; // int64 per rank in the all-gather's agreement (ag_agree)
 
 int pmmg_hip_comm_init(pmmg_hip_ctx *c, int nranks, int rank, const void *id) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   if (nranks < 1 || rank < 0 || rank >= nranks || !id) {
     set_err(c, "comm_init: invalid arguments (nranks=%d rank=%d)", nranks, rank);
     return 0;
@@ -2484,9 +2435,7 @@ static int ag_agree(pmmg_hip_ctx *c, const long long *mine, std::vector<long lon
 int pmmg_hip_allgather_points(pmmg_hip_ctx *c, const int64_t *counts, int nslot, const int *slot_size,
                               const double *const *rows, double *const *rows_all, const int *elem, int *elem_all,
                               const int8_t *hit, int8_t *hit_all) {
-  if (!c) return 0;
-  HIPCK(c, hipSetDevice(c->device));
-  if (!snap_join(c)) return 0;
+  if (!enter(c)) return 0;
   if (!c->comm) {
     set_err(c, "allgather_points: no communicator (pmmg_hip_comm_init / pmmg_hip_comm_attach)");
     return 0;

@@ -22,12 +22,12 @@
 // partials in a slab that one block adds in a fixed order, so two calls on
 // the same inputs return the same bytes.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "pmmg_meshstats.hpp"
+#include "pmmg_devutil.hpp"
 #include "pmmg_quality.hpp"
 
 namespace {
@@ -427,76 +427,40 @@ __global__ __launch_bounds__(kSBlock) void k_list_scatter(const double *xyz, int
 
 // ---------------------------------------------------------------- host side
 
-template <class T>
-T *slot(StatsCache *c, int i, size_t count) {
-  const size_t bytes = count * sizeof(T) > 0 ? count * sizeof(T) : 16;
-  if (c->cap[i] < bytes) {
-    if (c->p[i]) (void)hipFree(c->p[i]);
-    c->p[i] = nullptr;
-    c->cap[i] = 0;
-    if (hipMalloc(&c->p[i], bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    c->cap[i] = bytes;
-  }
-  return static_cast<T *>(c->p[i]);
-}
-
-enum { S_KEYS, S_OWN, S_SMALL, S_SLAB, S_MASK, S_RES, S_BTOT, S_BOFF, S_SCAN };
-
-#define MCK(expr)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) {                                                                         \
-      snprintf(msg, msglen, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return 0;                                                                                     \
-    }                                                                                               \
-  } while (0)
-
 int grid_of(long long n) {
   const long long need = (n + kSBlock - 1) / kSBlock;
   return (int)(need < 1 ? 1 : (need < kMaxGrid ? need : kMaxGrid));
 }
 
-constexpr int kSmallCnt = 32; // S_SMALL: 32 counters, then the 2 flags
+constexpr int kSmallCnt = 32; // StatsCache::small: 32 counters, then the 2 flags
 
 } // namespace
-
-void pmmg_stats_cache_free(StatsCache *c) {
-  if (!c) return;
-  for (int i = 0; i < StatsCache::kSlots; i++) {
-    if (c->p[i]) (void)hipFree(c->p[i]);
-    c->p[i] = nullptr;
-    c->cap[i] = 0;
-  }
-  c->grown_nslot = 0;
-}
 
 int64_t pmmg_stats_cache_bytes(const StatsCache *c) {
   int64_t b = 0;
   if (c)
-    for (int i = 0; i < StatsCache::kSlots; i++) b += (int64_t)c->cap[i];
+    for (const DevBuf *d : {&c->keys, &c->own, &c->small, &c->slab, &c->mask, &c->res, &c->btot, &c->boff, &c->scan})
+      b += (int64_t)d->cap;
   return b;
 }
 
 int pmmg_stats_qual_histo(hipStream_t s, int ne, const int *tetv, const double *qual, pmmg_hip_qual_histo_t *out,
                           StatsCache *cache, char *msg, size_t msglen) {
   const int nblk = grid_of(ne);
-  unsigned long long *cnt = slot<unsigned long long>(cache, S_SMALL, kSmallCnt + 2);
-  Part *slab = slot<Part>(cache, S_SLAB, (size_t)kMaxGrid);
-  pmmg_hip_qual_histo_t *res = reinterpret_cast<pmmg_hip_qual_histo_t *>(slot<char>(cache, S_RES, 512));
+  unsigned long long *cnt = get<unsigned long long>(cache->small, kSmallCnt + 2);
+  Part *slab = get<Part>(cache->slab, (size_t)kMaxGrid);
+  pmmg_hip_qual_histo_t *res = reinterpret_cast<pmmg_hip_qual_histo_t *>(get<char>(cache->res, 512));
   if (!cnt || !slab || !res) {
     snprintf(msg, msglen, "qual_histo: out of device memory");
     return 0;
   }
-  MCK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * (kSmallCnt + 2), s));
+  DEVCK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * (kSmallCnt + 2), s));
   hipLaunchKernelGGL(k_qual_histo, dim3(nblk), dim3(kSBlock), 0, s, ne, reinterpret_cast<const int4 *>(tetv), qual,
                      slab, cnt);
   hipLaunchKernelGGL(k_qual_final, dim3(1), dim3(kSBlock), 0, s, slab, nblk, cnt, res);
-  MCK(hipGetLastError());
-  MCK(hipMemcpyAsync(out, res, sizeof(*out), hipMemcpyDeviceToHost, s));
-  MCK(hipStreamSynchronize(s));
+  DEVCK(hipGetLastError());
+  DEVCK(hipMemcpyAsync(out, res, sizeof(*out), hipMemcpyDeviceToHost, s));
+  DEVCK(hipStreamSynchronize(s));
   return 1;
 }
 
@@ -524,10 +488,10 @@ int pmmg_stats_edge_lengths(hipStream_t s, int np, const double *xyz, int ne, co
       cache->grown_nslot > nslot)
     nslot = cache->grown_nslot; // (the size the last call on a mesh of these counts had to grow to)
   const int nblk = grid_of(ne);
-  unsigned long long *cnt = slot<unsigned long long>(cache, S_SMALL, kSmallCnt + 2);
-  Part *slab = slot<Part>(cache, S_SLAB, (size_t)kMaxGrid);
-  unsigned char *mask = slot<unsigned char>(cache, S_MASK, (size_t)ne);
-  pmmg_hip_len_histo_t *res = reinterpret_cast<pmmg_hip_len_histo_t *>(slot<char>(cache, S_RES, 512));
+  unsigned long long *cnt = get<unsigned long long>(cache->small, kSmallCnt + 2);
+  Part *slab = get<Part>(cache->slab, (size_t)kMaxGrid);
+  unsigned char *mask = get<unsigned char>(cache->mask, (size_t)ne);
+  pmmg_hip_len_histo_t *res = reinterpret_cast<pmmg_hip_len_histo_t *>(get<char>(cache->res, 512));
   if (!cnt || !slab || !mask || !res) {
     snprintf(msg, msglen, "edge_lengths: out of device memory");
     return 0;
@@ -539,8 +503,8 @@ int pmmg_stats_edge_lengths(hipStream_t s, int np, const double *xyz, int ne, co
       snprintf(msg, msglen, "edge_lengths: the edge table would exceed 2^32 slots");
       return 0;
     }
-    T.keys = slot<unsigned long long>(cache, S_KEYS, (size_t)nslot);
-    T.own = slot<unsigned int>(cache, S_OWN, (size_t)nslot);
+    T.keys = get<unsigned long long>(cache->keys, (size_t)nslot);
+    T.own = get<unsigned int>(cache->own, (size_t)nslot);
     if (!T.keys || !T.own) {
       snprintf(msg, msglen, "edge_lengths: out of device memory (edge table of %lld slots)", nslot);
       return 0;
@@ -549,17 +513,17 @@ int pmmg_stats_edge_lengths(hipStream_t s, int np, const double *xyz, int ne, co
     T.limit = nslot >= final_slots ? T.nslot : (T.nslot < kProbeLimit ? T.nslot : kProbeLimit);
     T.per = 0; // (mode 1 below the final size only: its stepped sequence need not visit every slot)
     if (hash_mode == 1 && nslot < final_slots) T.per = nslot / np > 1 ? (unsigned int)(nslot / np) : 1u;
-    MCK(hipMemsetAsync(T.keys, 0xff, sizeof(unsigned long long) * (size_t)nslot, s));
-    MCK(hipMemsetAsync(T.own, 0xff, sizeof(unsigned int) * (size_t)nslot, s));
-    MCK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * (kSmallCnt + 2), s));
+    DEVCK(hipMemsetAsync(T.keys, 0xff, sizeof(unsigned long long) * (size_t)nslot, s));
+    DEVCK(hipMemsetAsync(T.own, 0xff, sizeof(unsigned int) * (size_t)nslot, s));
+    DEVCK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * (kSmallCnt + 2), s));
     if (nskip > 0)
       hipLaunchKernelGGL(k_edge_skip, dim3(grid_of(nskip)), dim3(kSBlock), 0, s, T, np, nskip,
                          reinterpret_cast<const int2 *>(skip), flags);
     hipLaunchKernelGGL(k_edge_own, dim3(nblk), dim3(kSBlock), 0, s, T, np, ne, tv, flags);
-    MCK(hipGetLastError());
+    DEVCK(hipGetLastError());
     int h_flags[2] = {0, 0};
-    MCK(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, s));
-    MCK(hipStreamSynchronize(s));
+    DEVCK(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, s));
+    DEVCK(hipStreamSynchronize(s));
     if (h_flags[F_BADID]) {
       snprintf(msg, msglen, "edge_lengths: a used tetra has a vertex id outside [1, %d]", np);
       return 0;
@@ -578,9 +542,9 @@ int pmmg_stats_edge_lengths(hipStream_t s, int np, const double *xyz, int ne, co
   }
   hipLaunchKernelGGL(k_edge_analyse, dim3(nblk), dim3(kSBlock), 0, s, T, xyz, ne, tv, ani, met, mask, slab, cnt);
   hipLaunchKernelGGL(k_edge_final, dim3(1), dim3(kSBlock), 0, s, slab, nblk, cnt, tv, res);
-  MCK(hipGetLastError());
-  MCK(hipMemcpyAsync(out, res, sizeof(*out), hipMemcpyDeviceToHost, s));
-  MCK(hipStreamSynchronize(s));
+  DEVCK(hipGetLastError());
+  DEVCK(hipMemcpyAsync(out, res, sizeof(*out), hipMemcpyDeviceToHost, s));
+  DEVCK(hipStreamSynchronize(s));
   if (!edge_out && !len_out) return 1;
   const long long nlist = (long long)(out->nedge - out->nskipped);
   if (nlist > cap) {
@@ -590,23 +554,16 @@ int pmmg_stats_edge_lengths(hipStream_t s, int np, const double *xyz, int ne, co
   }
   if (ne == 0) return 1;
   const int lblk = (ne + kSBlock - 1) / kSBlock;
-  int *btot = slot<int>(cache, S_BTOT, (size_t)lblk), *boff = slot<int>(cache, S_BOFF, (size_t)lblk);
+  int *btot = get<int>(cache->btot, (size_t)lblk), *boff = get<int>(cache->boff, (size_t)lblk);
   if (!btot || !boff) {
     snprintf(msg, msglen, "edge_lengths: out of device memory (list pass)");
     return 0;
   }
   hipLaunchKernelGGL(k_list_count, dim3(lblk), dim3(kSBlock), 0, s, ne, mask, btot);
-  size_t tb = 0;
-  MCK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, btot, boff, lblk, s));
-  void *tmp = slot<char>(cache, S_SCAN, tb);
-  if (!tmp) {
-    snprintf(msg, msglen, "edge_lengths: out of device memory (scan)");
-    return 0;
-  }
-  MCK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, btot, boff, lblk, s));
+  if (!exclusive_scan(cache->scan, btot, boff, lblk, s, msg, msglen)) return 0;
   hipLaunchKernelGGL(k_list_scatter, dim3(lblk), dim3(kSBlock), 0, s, xyz, ne, tv, ani, met, mask, boff, cap,
                      reinterpret_cast<int2 *>(edge_out), len_out);
-  MCK(hipGetLastError());
-  MCK(hipStreamSynchronize(s));
+  DEVCK(hipGetLastError());
+  DEVCK(hipStreamSynchronize(s));
   return 1;
 }

@@ -7,19 +7,21 @@
 #include <stdint.h>
 
 #include "parmmg_hip.h"
+#include "pmmg_devbuf.hpp"
 
 // Device scratch of the two reports, owned by a context and kept between
 // calls (grown, never shrunk): the edge table, the ownership bytes, the
-// per-block slabs.  Freed by pmmg_stats_cache_free (pmmg_hip_release_scratch).
+// per-block slabs.
 struct StatsCache {
-  static constexpr int kSlots = 9;
-  void *p[kSlots] = {};
-  size_t cap[kSlots] = {};
+  DevBuf keys, own;  // the edge table: keys and owner codes
+  DevBuf small;      // 32 counters, then the 2 flags
+  DevBuf slab, mask; // per-block partials; the tetra's owned-edge bits
+  DevBuf res;        // the report on the device
+  DevBuf btot, boff, scan; // list pass: per-block counts, their offsets, the scan's temporary
   // the table size a call had to grow to, and the counts it was for: the next call on such a mesh starts there
   long long grown_nslot = 0;
   int grown_np = 0, grown_ne = 0, grown_nskip = 0, grown_mode = 0;
 };
-void pmmg_stats_cache_free(StatsCache *c);
 int64_t pmmg_stats_cache_bytes(const StatsCache *c);
 
 // pmmg_hip_qual_histo: device pointers (tetv 16-byte aligned), *out on the

@@ -32,13 +32,13 @@
 // two buckets in HBM, 9.3 of the 22 ms, latency-bound).  Scratch buffers are
 // kept by the context (SnapCache).
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <stdint.h>
 #include <stdio.h>
 
 
 #include "pmmg_snapshot.hpp"
+#include "pmmg_devutil.hpp"
 
 namespace {
 
@@ -444,119 +444,60 @@ __global__ __launch_bounds__(kB) void k_edge_match(const int *triv, int nt, cons
 
 int blocks(long long n) { return (int)((n + kB - 1) / kB > 0 ? (n + kB - 1) / kB : 1); }
 
-// device scratch: slot i of the context's cache (grown, never shrunk), or a
-// temporary freed at the end of the call when there is no cache
-struct Scratch {
-  SnapCache *cache;
-  void *tmp[SnapCache::kSlots] = {};
-  explicit Scratch(SnapCache *c) : cache(c) {}
-  ~Scratch() {
-    for (void *q : tmp)
-      if (q) (void)hipFree(q);
-  }
-  template <class T>
-  T *get(int slot, size_t count) {
-    const size_t bytes = count * sizeof(T) > 0 ? count * sizeof(T) : 16;
-    if (cache) {
-      if (cache->cap[slot] < bytes) {
-        if (cache->p[slot]) (void)hipFree(cache->p[slot]);
-        cache->p[slot] = nullptr;
-        cache->cap[slot] = 0;
-        if (hipMalloc(&cache->p[slot], bytes) != hipSuccess) return nullptr;
-        cache->cap[slot] = bytes;
-      }
-      return static_cast<T *>(cache->p[slot]);
-    }
-    if (tmp[slot]) (void)hipFree(tmp[slot]);
-    tmp[slot] = nullptr;
-    if (hipMalloc(&tmp[slot], bytes) != hipSuccess) return nullptr;
-    return static_cast<T *>(tmp[slot]);
-  }
-};
-
-#define SCK(expr)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) {                                                                         \
-      snprintf(msg, msglen, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return 0;                                                                                     \
-    }                                                                                               \
-  } while (0)
-
-constexpr int kSlotScan = SnapCache::kSlots - 1;
-int exclusive_scan(Scratch &S, const int *in, int *out, int n, hipStream_t s, char *msg, size_t msglen) {
-  size_t tb = 0;
-  SCK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, s));
-  void *tmp = S.get<char>(kSlotScan, tb);
-  if (!tmp) { snprintf(msg, msglen, "out of device memory (scan)"); return 0; }
-  SCK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, n, s));
-  return 1;
-}
-
 } // namespace
 
 int pmmg_snap_adjacency(hipStream_t s, int np, int ne, const int *tetv, int *adja, int *tet8, SnapCache *cache,
                         char *msg, size_t msglen) {
-  Scratch S(cache);
   const long long nf = 4LL * ne;
-  int *cnt = S.get<int>(0, (size_t)np), *off = S.get<int>(1, (size_t)np), *err = S.get<int>(2, 1);
-  int *cursor = S.get<int>(3, (size_t)np);
-  int3 *bucket = S.get<int3>(4, (size_t)nf); // {b, c, code} of every face
+  int *cnt = get<int>(cache->cnt, (size_t)np), *off = get<int>(cache->off, (size_t)np), *err = get<int>(cache->err, 1);
+  int *cursor = get<int>(cache->cursor, (size_t)np);
+  int3 *bucket = get<int3>(cache->bucket, (size_t)nf); // {b, c, code} of every face
   if (!cnt || !off || !cursor || !err || !bucket) {
     snprintf(msg, msglen, "build_adjacency: out of device memory (%lld faces)", nf);
     return 0;
   }
-  SCK(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)np, s));
-  SCK(hipMemsetAsync(err, 0, sizeof(int), s));
+  DEVCK(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)np, s));
+  DEVCK(hipMemsetAsync(err, 0, sizeof(int), s));
   const int4 *tv = reinterpret_cast<const int4 *>(tetv);
   hipLaunchKernelGGL(k_face_count, dim3(blocks(ne)), dim3(kB), 0, s, tv, ne, np, cnt, reinterpret_cast<int4 *>(tet8),
                      err);
-  if (!exclusive_scan(S, cnt, off, np, s, msg, msglen)) return 0;
-  SCK(hipMemcpyAsync(cursor, off, sizeof(int) * (size_t)np, hipMemcpyDeviceToDevice, s));
+  if (!exclusive_scan(cache->scan, cnt, off, np, s, msg, msglen)) return 0;
+  DEVCK(hipMemcpyAsync(cursor, off, sizeof(int) * (size_t)np, hipMemcpyDeviceToDevice, s));
   hipLaunchKernelGGL(k_face_scatter, dim3(blocks(ne)), dim3(kB), 0, s, tv, ne, np, cursor, bucket,
                      reinterpret_cast<int4 *>(adja), reinterpret_cast<int4 *>(tet8));
   hipLaunchKernelGGL(k_face_match, dim3((np + kMatchVerts - 1) / kMatchVerts), dim3(kB), 0, s, np, off, cnt, bucket,
                      adja, tet8, err);
-  SCK(hipGetLastError());
+  DEVCK(hipGetLastError());
   int h_err = 0;
-  SCK(hipMemcpyAsync(&h_err, err, sizeof(int), hipMemcpyDeviceToHost, s));
-  SCK(hipStreamSynchronize(s));
+  DEVCK(hipMemcpyAsync(&h_err, err, sizeof(int), hipMemcpyDeviceToHost, s));
+  DEVCK(hipStreamSynchronize(s));
   if (h_err & kErrIds) { snprintf(msg, msglen, "build_adjacency: vertex ids out of [1, np] or repeated in a tetra"); return 0; }
   if (h_err & kErrNonManifold) { snprintf(msg, msglen, "build_adjacency: a face is shared by more than two tetra"); return 0; }
   return 1;
 }
 
-void pmmg_snap_cache_free(SnapCache *c) {
-  if (!c) return;
-  for (int i = 0; i < SnapCache::kSlots; i++) {
-    if (c->p[i]) (void)hipFree(c->p[i]);
-    c->p[i] = nullptr;
-    c->cap[i] = 0;
-  }
-}
-
 int pmmg_snap_tria_adjacency(hipStream_t s, int np, int nt, const int *triv, int *adjt, SnapCache *cache, char *msg,
                              size_t msglen) {
   if (nt == 0) return 1;
-  Scratch S(cache);
   const long long nedge = 3LL * nt;
-  int *cnt = S.get<int>(0, (size_t)np), *off = S.get<int>(1, (size_t)np), *rank = S.get<int>(3, (size_t)nedge);
-  int2 *bucket = S.get<int2>(4, (size_t)nedge);
-  int *err = S.get<int>(2, 1);
+  int *cnt = get<int>(cache->cnt, (size_t)np), *off = get<int>(cache->off, (size_t)np);
+  int *rank = get<int>(cache->cursor, (size_t)nedge);
+  int2 *bucket = get<int2>(cache->bucket, (size_t)nedge);
+  int *err = get<int>(cache->err, 1);
   if (!cnt || !off || !rank || !bucket || !err) {
     snprintf(msg, msglen, "tria adjacency: out of device memory");
     return 0;
   }
-  SCK(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)np, s));
-  SCK(hipMemsetAsync(err, 0, sizeof(int), s));
+  DEVCK(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)np, s));
+  DEVCK(hipMemsetAsync(err, 0, sizeof(int), s));
   hipLaunchKernelGGL(k_edge_count, dim3(blocks(nedge)), dim3(kB), 0, s, triv, nt, np, cnt, rank, err);
-  if (!exclusive_scan(S, cnt, off, np, s, msg, msglen)) return 0;
+  if (!exclusive_scan(cache->scan, cnt, off, np, s, msg, msglen)) return 0;
   hipLaunchKernelGGL(k_edge_scatter, dim3(blocks(nedge)), dim3(kB), 0, s, triv, nt, off, rank, bucket);
   hipLaunchKernelGGL(k_edge_match, dim3(blocks(nedge)), dim3(kB), 0, s, triv, nt, off, cnt, bucket, adjt);
-  SCK(hipGetLastError());
+  DEVCK(hipGetLastError());
   int h_err = 0;
-  SCK(hipMemcpyAsync(&h_err, err, sizeof(int), hipMemcpyDeviceToHost, s));
-  SCK(hipStreamSynchronize(s));
+  DEVCK(hipMemcpyAsync(&h_err, err, sizeof(int), hipMemcpyDeviceToHost, s));
+  DEVCK(hipStreamSynchronize(s));
   if (h_err) {
     snprintf(msg, msglen, "tria adjacency: tria vertex ids out of [1, np]");
     return 0;
@@ -567,26 +508,25 @@ int pmmg_snap_tria_adjacency(hipStream_t s, int np, int nt, const int *triv, int
 int pmmg_snap_boundary(hipStream_t s, int np, int ne, const int *tetv, int tstride, const int *adja, int astride,
                        const int *tref, int cap, int *nt_out, int *triv, int *adjt, SnapCache *cache, char *msg,
                        size_t msglen) {
-  Scratch S(cache);
   const int nblk = blocks(ne);
-  int *cand = S.get<int>(5, (size_t)nblk * kB), *bs = S.get<int>(6, 3 * (size_t)nblk);
+  int *cand = get<int>(cache->cand, (size_t)nblk * kB), *bs = get<int>(cache->blk, 3 * (size_t)nblk);
   if (!cand || !bs) { snprintf(msg, msglen, "build_boundary: out of device memory"); return 0; }
   int *btot = bs, *bcnt = bs + nblk, *boff = bs + 2 * (size_t)nblk;
   const int4 *tv = reinterpret_cast<const int4 *>(tetv), *ad = reinterpret_cast<const int4 *>(adja);
   hipLaunchKernelGGL(k_bdy_count, dim3(nblk), dim3(kB), 0, s, ad, astride, tref, ne, cand, btot, bcnt);
-  if (!exclusive_scan(S, btot, boff, nblk, s, msg, msglen)) return 0;
+  if (!exclusive_scan(cache->scan, btot, boff, nblk, s, msg, msglen)) return 0;
   int last[2] = {0, 0};
-  SCK(hipMemcpyAsync(&last[0], boff + nblk - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-  SCK(hipMemcpyAsync(&last[1], btot + nblk - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-  SCK(hipStreamSynchronize(s));
+  DEVCK(hipMemcpyAsync(&last[0], boff + nblk - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+  DEVCK(hipMemcpyAsync(&last[1], btot + nblk - 1, sizeof(int), hipMemcpyDeviceToHost, s));
+  DEVCK(hipStreamSynchronize(s));
   const int nt = last[0] + last[1];
   *nt_out = nt;
   if (nt > cap) { snprintf(msg, msglen, "build_boundary: %d boundary trias exceed the capacity %d", nt, cap); return 0; }
   if (nt == 0) return 1;
   hipLaunchKernelGGL(k_bdy_write, dim3(nblk), dim3(kB), 0, s, tv, tstride, ad, astride, tref, (const int *)cand,
                      (const int *)bcnt, (const int *)boff, triv);
-  SCK(hipGetLastError());
+  DEVCK(hipGetLastError());
   if (adjt && !pmmg_snap_tria_adjacency(s, np, nt, triv, adjt, cache, msg, msglen)) return 0;
-  SCK(hipStreamSynchronize(s));
+  DEVCK(hipStreamSynchronize(s));
   return 1;
 }

@@ -4,15 +4,18 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "pmmg_devbuf.hpp"
+
 // Device scratch of the snapshot kernels kept between calls (owned by a
-// context; hipMalloc / hipFree of the GB-sized face buckets every call cost
-// milliseconds and synchronise the device).  NULL: temporaries.
+// context, grown, never shrunk; hipMalloc / hipFree of the GB-sized face
+// buckets every call cost milliseconds and synchronise the device).
 struct SnapCache {
-  static constexpr int kSlots = 8;
-  void *p[kSlots] = {};
-  size_t cap[kSlots] = {};
+  DevBuf cnt, off, err; // per-vertex bucket sizes and offsets, the error bits
+  DevBuf cursor;        // the buckets' cursors (tetra faces) or the edges' ranks (tria edges)
+  DevBuf bucket;        // the face / edge buckets
+  DevBuf cand, blk;     // boundary pass: candidate tetra, the per-block {total, count, offset}
+  DevBuf scan;          // the scan's temporary
 };
-void pmmg_snap_cache_free(SnapCache *c);
 
 // adja[4*ne] (may be NULL) and/or tet8[8*ne] (may be NULL) from tetv[4*ne];
 // all device pointers, 16-byte aligned.  Returns 1, or 0 with msg set.

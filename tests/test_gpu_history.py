@@ -14,7 +14,14 @@ n_old = 57 (1,111,158 tetra, 38,988 trias) is the smallest to reach that
 ng_clr == 0 with fewer cells), A, A with a point map that covers every point
 (the volume grid is neither filled nor read, and refilled all the same), A
 executes every combination of clean / dirty and larger / smaller; each call
-is bit-identical to its fresh-context run."""
+is bit-identical to its fresh-context run.
+
+test_every_buffer_family_then_destroy: a context that has used every family
+of device buffers it owns (copies of host inputs, a device-built background,
+host-mode staging, field vectors that shrink, two kept slots and a consumed
+carry-over, packed records, a point map and its start tables, group lanes, the
+reports' and the graph's scratch) is destroyed as it stands, and the next
+context of the process starts from nothing."""
 import numpy as np
 import pytest
 
@@ -142,6 +149,129 @@ def test_call_sequence(seq_cases, sort):
             except AssertionError as e:
                 raise AssertionError(f"call {i} ({name}) differs from its fresh-context run: {e}") from e
             assert_skipped_keep(K[name], got)
+
+
+# ---------------------------------------------------------------- every buffer family, then destroy
+
+def host_built(ctx, xyz, tetv, met, fields, new_xyz, pclass, hausd):
+    """one host-mode call whose adjacency and boundary trias are built on the
+    device (adja absent, nt < 0)"""
+    ctx.set_background(xyz, tetv, None, None, None, hausd)
+    ctx.set_solutions(met, fields)
+    n = new_xyz.shape[0]
+    mo = None if met is None else np.full((n, met.shape[1]), np.nan)
+    fo = [np.full((n, f.shape[1]), np.nan) for f in fields]
+    el, hit = np.zeros(n, np.int32), np.zeros(n, np.int8)
+    st = ctx.locate_interp(new_xyz, pclass, mo, fo, el, hit)
+    return dict(met=mo, fields=fo, elem=el, hit=hit, stats=dict(st.as_dict(), reserved=list(st.reserved)))
+
+
+def run_reports(ctx, case):
+    """tetra_qual, qual_histo and edge_lengths (with its lists) of a case's background"""
+    d = [ctx.upload(case["bg"].xyz), ctx.upload(case["bg"].tetv), ctx.upload(case["met"])]
+    qual, mn = ctx.tetra_qual(d[0], d[1], d[2])
+    histo = ctx.qual_histo(d[1], qual)
+    lens, edges, ll = ctx.edge_lengths(d[0], d[1], d[2], want_edges=True)
+    out = dict(qual=qual.download(), minqual=mn, histo=histo, lens=lens, edges=edges.download(), ll=ll.download())
+    for a in d + [qual, edges, ll]:
+        a.free()
+    return out
+
+
+def run_graph(ctx, case):
+    """metis_graph with the adjacency built on the device"""
+    d = [ctx.upload(case["bg"].xyz), ctx.upload(case["bg"].tetv), ctx.upload(case["met"])]
+    g = ctx.metis_graph(d[0], d[1], met=d[2])
+    out = [a.download() for a in g]
+    for a in d + list(g):
+        a.free()
+    return out
+
+
+def same_report(a, b):
+    assert a.keys() == b.keys()
+    for key in a:
+        if isinstance(a[key], np.ndarray):
+            np.testing.assert_array_equal(a[key].view(np.uint8), b[key].view(np.uint8), err_msg=key)
+        else:
+            assert repr(a[key]) == repr(b[key]), (key, a[key], b[key])  # (repr: NaN equal to itself, -0.0 not to 0.0)
+
+
+@pytest.mark.gpu
+def test_every_buffer_family_then_destroy(seq_cases):
+    """On one context: a host-mode call on a device-built background with a
+    metric and two fields, kept in slot 0; a host-mode call with one scalar
+    field (the field vectors shrink from two to one), kept in slot 1; slot 0
+    carried into the next host-mode background and solutions; packed records;
+    a point map; two groups; the two reports; the element graph on a
+    device-built adjacency.  Every call equals the same call on a fresh
+    context.  The context is then destroyed without release_scratch, with
+    every buffer family live, and a new context repeats the first call."""
+    K = seq_cases
+    first = make_case(kind=C, n_old=6, n_new=7, fields=(synth.F_SCALAR, synth.F_VECTOR), req_every=5, with_ref=False)
+    iso = K["iso"]
+    nxt = make_case(kind=C, n_old=6, n_new=8, req_every=7, with_ref=False)  # (its new points: the carried call's)
+    A = first["new"]
+
+    def call_first(ctx):
+        return host_built(ctx, first["bg"].xyz, first["bg"].tetv, first["met"], first["fields"], A.xyz,
+                          first["pclass"], first["hausd"])
+
+    def call_iso(ctx):
+        return host_built(ctx, iso["bg"].xyz, iso["bg"].tetv, iso["met"], iso["fields"], iso["new"].xyz,
+                          iso["pclass"], iso["hausd"])
+
+    def call_carried(ctx, rows):
+        # the adapted mesh of the first call is the old mesh now; the host holds the rows the step wrote and
+        # fills the others (skipped points) itself
+        met, fields = rows["met"].copy(), [f.copy() for f in rows["fields"]]
+        skip = np.isnan(met[:, 0])
+        met[skip] = [1.0, 0.0, 0.0, 1.0, 0.0, 1.0]
+        for f in fields:
+            f[np.isnan(f[:, 0])] = -2.0
+        return host_built(ctx, A.xyz, A.tetv, met, fields, nxt["new"].xyz, nxt["pclass"], first["hausd"])
+
+    with TransferContext(0) as ctx:
+        f_first = call_first(ctx)
+    assert (first["pclass"] == 0).any() and np.isnan(f_first["met"][first["pclass"] == 0]).all()
+    assert f_first["stats"]["nvol"] > 0 and f_first["stats"]["nbdy"] > 0
+    fresh = dict(first=f_first)
+    for name, fn in (("iso", call_iso), ("carried", lambda c: call_carried(c, f_first)),
+                     ("packed", lambda c: run_gpu(K["packed"], ctx=c, tet8=True, packed=True)),
+                     ("mapped", lambda c: run_mapped(K["mapped"], c, K["mapped"]["src"])),
+                     ("groups", lambda c: run_groups(K["groups"], c)),
+                     ("reports", lambda c: run_reports(c, K["shell"])),
+                     ("graph", lambda c: run_graph(c, K["shell"]))):
+        with TransferContext(0) as ctx:
+            fresh[name] = fn(ctx)
+    assert fresh["carried"]["stats"]["nvol"] > 0 and fresh["mapped"]["stats"]["nvol_src"] > 0
+    assert fresh["reports"]["lens"]["nedge"] > 0 and fresh["graph"][0][-1] > 0
+
+    ctx = TransferContext(0)
+    try:
+        same_call(call_first(ctx), fresh["first"])
+        ctx.keep(0)
+        same_call(call_iso(ctx), fresh["iso"])
+        ctx.keep(1)
+        ctx.carry_over(0, A.np)
+        same_call(call_carried(ctx, fresh["first"]), fresh["carried"])
+        with pytest.raises(RuntimeError, match="holds nothing"):
+            ctx.carry_over(0, A.np)  # consumed by the call above
+        same_call(run_gpu(K["packed"], ctx=ctx, tet8=True, packed=True), fresh["packed"])
+        same_call(run_mapped(K["mapped"], ctx, K["mapped"]["src"]), fresh["mapped"])
+        outs, st = run_groups(K["groups"], ctx)
+        for a, b in zip(outs, fresh["groups"][0]):
+            same_outputs(a, b)
+        for key in COUNTERS:
+            assert st[key] == fresh["groups"][1][key], key
+        same_report(run_reports(ctx, K["shell"]), fresh["reports"])
+        for a, b in zip(run_graph(ctx, K["shell"]), fresh["graph"]):
+            np.testing.assert_array_equal(a, b)
+        assert ctx.mesh_stats_bytes() > 0
+    finally:
+        ctx.close()  # pmmg_hip_destroy, no release_scratch before it
+    with TransferContext(0) as ctx:
+        same_call(call_first(ctx), fresh["first"])
 
 
 # ---------------------------------------------------------------- refilled seed grids
