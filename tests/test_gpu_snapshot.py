@@ -12,8 +12,13 @@ import numpy as np
 import pytest
 
 from parity import make_case, run_gpu
+from snapshot_ref import IDIR as _IDIR, MATCH_CAP, adjacency, tria_adjacency as _host_tria_adjacency
 from parmmg_amd import synth
 from parmmg_amd.transfer import TransferContext, pack_tet8
+
+
+def _host_adjacency(tetv):
+    return adjacency(tetv)[0]
 
 
 def _snapshot(ctx, bg, use_tet8=True):
@@ -60,30 +65,17 @@ def test_snapshot_of_a_shuffled_numbering():
         np.testing.assert_array_equal(adja.download(), expect)
 
 
-def _host_adjacency(tetv):
-    """MMG3D_hashTetra's result by a dictionary of sorted faces (face i opposite vertex i)."""
-    faces = {}
-    for k, t in enumerate(tetv.tolist()):
-        for i in range(4):
-            faces.setdefault(tuple(sorted(t[:i] + t[i + 1:])), []).append(4 * (k + 1) + i)
-    adja = np.zeros(tetv.shape, np.int32)
-    for codes in faces.values():
-        if len(codes) == 2:
-            a, b = codes
-            adja[a // 4 - 1, a % 4], adja[b // 4 - 1, b % 4] = b, a
-    return adja
-
-
 @pytest.mark.gpu
 def test_snapshot_of_a_high_valence_vertex():
     """A star of tetra around one vertex (vertex 1, the smallest id, in every
-    tetra): its face bucket holds 3 faces per tetra, more than the match
-    kernel stages in LDS for a block of vertices (kMatchCap, 768 entries), so
-    that block scans its buckets in place."""
+    tetra): its face bucket holds 3 faces per tetra, several times what the
+    match kernel stages in LDS for a block of vertices (kMatchCap, 768
+    entries), so that block scans its buckets in place, each thread more than
+    one entry (the sizes next to kMatchCap are in test_gpu_snapshot_meshes.py)."""
     bg = synth.lattice(synth.SHELL, 12)
     r = np.linalg.norm(bg.xyz - bg.xyz.mean(0), axis=1)
     outer = bg.triv[(r[bg.triv - 1] > np.median(r)).all(axis=1)]
-    assert 3 * outer.shape[0] > 2048  # pmmg_snapshot.hip kMatchCap
+    assert MATCH_CAP == 768 and 3 * outer.shape[0] > 2048 > 2 * MATCH_CAP  # pmmg_snapshot.hip kMatchCap
     tetv = np.hstack([np.ones((outer.shape[0], 1), np.int32), outer + 1]).astype(np.int32)
     with TransferContext(0) as ctx:
         adja, tet8 = ctx.build_adjacency(bg.np + 1, ctx.upload(np.ascontiguousarray(tetv)))
@@ -91,24 +83,6 @@ def test_snapshot_of_a_high_valence_vertex():
         np.testing.assert_array_equal(adja.download(), expect)
         np.testing.assert_array_equal(tet8.download(), pack_tet8(tetv, expect))
         assert (expect[:, 0] == 0).all() and (expect[:, 1:] > 0).all()  # the outer faces, the star's inner faces
-
-
-_IDIR = np.array([[1, 2, 3], [0, 3, 2], [0, 1, 3], [0, 2, 1]])
-
-
-def _host_tria_adjacency(triv):
-    """MMG3D_hashTria's adjt: edge j (opposite local vertex j) paired only
-    when exactly two trias share it"""
-    edges = {}
-    for t, tri in enumerate(triv.tolist()):
-        for j in range(3):
-            edges.setdefault(tuple(sorted((tri[(j + 1) % 3], tri[(j + 2) % 3]))), []).append(3 * (t + 1) + j)
-    adjt = np.zeros(triv.shape, np.int32)
-    for codes in edges.values():
-        if len(codes) == 2:
-            a, b = codes
-            adjt[a // 3 - 1, a % 3], adjt[b // 3 - 1, b % 3] = b, a
-    return adjt
 
 
 @pytest.mark.gpu
