@@ -65,7 +65,8 @@ def build_hip(force: bool = False) -> str:
         os.path.join(CSRC, h) for h in ("pmmg_device.hpp", "pmmg_prep.hpp", "pmmg_vol.hpp", "pmmg_bdy.hpp",
                                         "pmmg_fallback.hpp", "pmmg_snapshot.hpp", "pmmg_quality.hpp",
                                         "pmmg_meshstats.hpp", "pmmg_graph.hpp", "pmmg_sort.hpp", "pmmg_comm.hpp",
-                                        "pmmg_devbuf.hpp", "pmmg_devutil.hpp")]
+                                        "pmmg_devbuf.hpp", "pmmg_devutil.hpp", "pmmg_ctx.hpp", "pmmg_xfer.hpp",
+                                        "pmmg_carry.hpp", "pmmg_call.hpp", "pmmg_groups.hpp")]
     if force or _stale(out, deps):
         # max-memory-clause scheduling: the gathers of a step issued as clauses
         # (volume kernel -4.6 % at cfg4, same registers; profiles/r02e/sweep_sched_strategy.txt)

@@ -14,11 +14,14 @@
 // of R = 8 K + 8 bytes (K doubles, int32 element, int8 hit, padding) in a
 // send buffer of max_r counts[r] records, one ncclAllGather of that many
 // bytes per rank (ring over xGMI), then one kernel unpacks every rank's
-// records into the rank-order concatenation of the caller's output arrays.
+// records into the rank-order concatenation of the caller's output arrays
+// (after the loader and the kernels: ag_agree and ag_points, the host side).
 #pragma once
 
 #include <dlfcn.h>
 #include <rccl/rccl.h> // types only: the functions are taken from the dlopen'ed library
+
+#include "pmmg_ctx.hpp"
 
 namespace pmmg {
 
@@ -98,3 +101,135 @@ __global__ __launch_bounds__(kBlock) void k_ag_unpack(AgSlots S, const char *rec
 }
 
 } // namespace pmmg
+
+static void comm_release(pmmg_hip_ctx *c) {
+  if (c->comm && c->comm_owned && rccl().ok) (void)rccl().commDestroy(c->comm);
+  c->comm = nullptr;
+  c->comm_owned = false;
+  c->comm_rank = c->comm_size = 0;
+}
+
+static constexpr int kAgView = 8; // int64 per rank in the all-gather's agreement (ag_agree)
+
+// The all-gather's agreement: every rank that holds a
+// communicator takes part in one small all-gather of its view of the call —
+// {local arguments valid and buffers allocated, K, nslot, the slot sizes, elem
+// / hit given, a hash of counts[]} — before the data collective, and every
+// rank then takes the same decision: either all gather, or all return 0 (a
+// rank that returned early used to leave the others inside ncclAllGather, and
+// records of different sizes R = 8 K + 8 were undefined behaviour).
+static int ag_agree(pmmg_hip_ctx *c, const long long *mine, std::vector<long long> &all) {
+  const int N = c->comm_size;
+  all.assign((size_t)kAgView * N, 0);
+  if (!ensure(c, c->ag_chk, sizeof(long long) * kAgView * (N + 1))) return 0;
+  long long *d = c->ag_chk.as<long long>();
+  hipStream_t s = c->stream;
+  HIPCK(c, hipMemcpyAsync(d, mine, sizeof(long long) * kAgView, hipMemcpyHostToDevice, s));
+  const ncclResult_t e = rccl().allGather(d, d + kAgView, kAgView, ncclInt64, c->comm, s);
+  if (e != ncclSuccess) {
+    set_err(c, "ncclAllGather (agreement): %s", rccl().errorString(e));
+    return 0;
+  }
+  HIPCK(c, hipMemcpyAsync(all.data(), d + kAgView, sizeof(long long) * kAgView * N, hipMemcpyDeviceToHost, s));
+  HIPCK(c, hipStreamSynchronize(s));
+  return 1;
+}
+
+// pmmg_hip_allgather_points on a context whose device is current
+static int ag_points(pmmg_hip_ctx *c, const int64_t *counts, int nslot, const int *slot_size,
+                     const double *const *rows, double *const *rows_all, const int *elem, int *elem_all,
+                     const int8_t *hit, int8_t *hit_all) {
+  if (!c->comm) {
+    set_err(c, "allgather_points: no communicator (pmmg_hip_comm_init / pmmg_hip_comm_attach)");
+    return 0;
+  }
+  const int N = c->comm_size;
+  // local checks: a failure is recorded (ok = 0), not returned, so that this
+  // rank still takes part in the agreement below
+  bool ok = true;
+  char why[256] = {0};
+  if (!counts || nslot < 0 || nslot > kMaxSlot || (nslot > 0 && (!slot_size || !rows || !rows_all)) ||
+      (!elem) != (!elem_all) || (!hit) != (!hit_all)) {
+    snprintf(why, sizeof(why), "allgather_points: invalid arguments (nslot=%d)", nslot);
+    ok = false;
+  }
+  AgSlots S{};
+  long long sizes_code = 0;
+  if (ok) {
+    S.n = nslot;
+    for (int j = 0; j < nslot && ok; j++) {
+      if (slot_size[j] < 1 || slot_size[j] > 6 || !rows_all[j] || (counts[c->comm_rank] > 0 && !rows[j])) {
+        snprintf(why, sizeof(why), "allgather_points: slot %d (size %d) invalid", j, slot_size[j]);
+        ok = false;
+        break;
+      }
+      S.in[j] = rows[j];
+      S.out[j] = rows_all[j];
+      S.size[j] = slot_size[j];
+      S.K += slot_size[j];
+      sizes_code = sizes_code * 8 + slot_size[j];
+    }
+  }
+  std::vector<long long> off((size_t)N + 1, 0);
+  long long maxn = 0;
+  unsigned long long chash = 0x9E3779B97F4A7C15ULL;
+  for (int r = 0; r < N && ok; r++) {
+    if (counts[r] < 0) {
+      snprintf(why, sizeof(why), "allgather_points: counts[%d] = %lld", r, (long long)counts[r]);
+      ok = false;
+      break;
+    }
+    off[r + 1] = off[r] + counts[r];
+    maxn = std::max(maxn, (long long)counts[r]);
+    chash = (chash ^ (unsigned long long)counts[r]) * 0x100000001B3ULL;
+  }
+  const long long R = 8LL * S.K + 8;
+  if (ok && maxn > 0 &&
+      (!ensure(c, c->ag_send, (size_t)(R * maxn)) || !ensure(c, c->ag_recv, (size_t)(R * maxn * N)) ||
+       !ensure(c, c->ag_off, sizeof(long long) * off.size()))) {
+    snprintf(why, sizeof(why), "allgather_points: buffers: %s", c->err);
+    ok = false;
+  }
+  // the arguments that must be identical on every rank: nslot, slot_size[],
+  // whether elem / hit are given, counts[] (hence K, R and maxn)
+  const long long mine[kAgView] = {ok ? 1 : 0, S.K, nslot, sizes_code, elem ? 1 : 0, hit ? 1 : 0,
+                                   (long long)(chash >> 1), maxn};
+  std::vector<long long> all;
+  if (!ag_agree(c, mine, all)) return 0;
+  if (!ok) {
+    set_err(c, "%s", why);
+    return 0;
+  }
+  for (int r = 0; r < N; r++) {
+    const long long *v = &all[(size_t)kAgView * r];
+    if (!v[0]) {
+      set_err(c, "allgather_points: rank %d's arguments are invalid", r);
+      return 0;
+    }
+    for (int j = 1; j < kAgView; j++)
+      if (v[j] != all[j]) {
+        set_err(c, "allgather_points: rank %d disagrees with rank 0 on %s", r,
+                j <= 3 ? "the slot layout" : (j <= 5 ? "elem / hit" : "counts[]"));
+        return 0;
+      }
+  }
+  const long long n = counts[c->comm_rank];
+  if (maxn == 0) return 1;
+  hipStream_t s = c->stream;
+  HIPCK(c, hipMemcpyAsync(c->ag_off.p, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice, s));
+  if (n > 0)
+    hipLaunchKernelGGL(k_ag_pack, dim3(blocks_for(n, 4096)), dim3(kBlock), 0, s, S, elem, hit, n,
+                       c->ag_send.as<char>());
+  HIPCK(c, hipGetLastError());
+  const ncclResult_t e =
+      rccl().allGather(c->ag_send.p, c->ag_recv.p, (size_t)(R * maxn), ncclInt8, c->comm, s);
+  if (e != ncclSuccess) {
+    set_err(c, "ncclAllGather: %s", rccl().errorString(e));
+    return 0;
+  }
+  hipLaunchKernelGGL(k_ag_unpack, dim3(blocks_for(off[N], 8192)), dim3(kBlock), 0, s, S, c->ag_recv.as<const char>(),
+                     maxn, N, c->ag_off.as<const long long>(), elem_all, hit_all);
+  HIPCK(c, hipGetLastError());
+  HIPCK(c, hipStreamSynchronize(s));
+  return 1;
+}

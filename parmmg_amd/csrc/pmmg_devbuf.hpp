@@ -40,6 +40,9 @@ struct DevBuf {
   }
   ~DevBuf() { release(); }
 
+  template <class T> // the block as elements of T (no allocation: nullptr while the buffer is empty)
+  T *as() const { return static_cast<T *>(p); }
+
   void release() {
     if (p) (void)PMMG_DEV_FREE(p);
     p = nullptr;

@@ -244,17 +244,6 @@ __device__ __forceinline__ bool before(double va, int a, double vb, int b) {
   return (va < vb) || (va == vb && a < b);
 }
 
-__device__ __forceinline__ void ranks4(const double *b, int *r) {
-#pragma unroll
-  for (int f = 0; f < 4; f++) {
-    int c = 0;
-#pragma unroll
-    for (int g = 0; g < 4; g++)
-      if (g != f && before(b[g], g, b[f], f)) c++;
-    r[f] = c;
-  }
-}
-
 __device__ __forceinline__ void ranks3(const double *b, int *r) {
 #pragma unroll
   for (int f = 0; f < 3; f++) {

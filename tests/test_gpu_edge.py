@@ -7,10 +7,13 @@ tolerance 1e-13 absolute), a constant SPD tensor reproduced by the
 inverse-tensor interpolation, acceptance and values of a random sample
 checked against the oracle, and determinism across runs.
 """
+import dataclasses
+import functools
+
 import numpy as np
 import pytest
 
-from parity import check, make_case, run_dev, run_gpu
+from parity import check, make_case, make_ctx, run_dev, run_gpu
 from parmmg_amd import configs, synth
 from parmmg_amd.transfer import TransferContext, pack_tet8
 
@@ -137,6 +140,52 @@ def test_full_size_cfg3_sample_against_oracle_and_determinism():
     assert rep["n"] == 3000 and rep["maxrel"] <= 1e-12
 
 
+STAGES_MS = ("ms_prepare", "ms_sort", "ms_vol", "ms_bdy", "ms_fallback")
+
+
+def _check_intervals(stats):
+    """The ms_* of one call's stats as intervals: finite and >= 0, and every
+    stage within the whole call (each lies between the call's first event and
+    its last, which waits for all streams)."""
+    ms = {k: float(v) for k, v in stats.items() if k.startswith("ms_")}
+    print(ms)
+    assert set(STAGES_MS) | {"ms_total", "ms_vol_locate"} <= set(ms)
+    for k, v in ms.items():
+        assert np.isfinite(v) and v >= 0, (k, v)
+    for k in STAGES_MS:
+        assert ms[k] <= ms["ms_total"], (k, ms)
+
+
+@functools.lru_cache(maxsize=None)
+def _intervals_case():
+    """64k new points on the 8^3 background: a small group (input order untested when the order is auto)."""
+    return make_case(kind=C, n_old=8, n_new=39, with_ref=False)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", ["input order", "Morton order", "auto order", "no trias", "point map", "two calls"])
+def test_stats_intervals_on_every_route(route):
+    """Every route through a call records the events its stats are read from:
+    the orders forced and chosen, a background without trias, a call with a
+    point map, and a second call on a context whose events still hold the
+    first call's records (a background without trias after one with)."""
+    case = _intervals_case()
+    notri = dict(case, bg=dataclasses.replace(case["bg"], triv=np.zeros((0, 3), np.int32),
+                                              adjt=np.zeros((0, 3), np.int32)),
+                 pclass=np.where(case["pclass"] == 2, 0, case["pclass"]).astype(np.uint8))
+    sort = {"input order": False, "Morton order": True}.get(route)
+    with make_ctx(sort) as ctx:
+        if route == "point map":
+            ctx.set_point_map(synth.point_map(case["bg"], case["new"].xyz))
+        runs = {"no trias": [notri], "two calls": [case, notri]}.get(route, [case])
+        for one in runs:
+            out = run_gpu(one, ctx=ctx)  # (a call that returns 0 raises)
+            assert ctx.error() == ""
+            assert out["stats"]["sorted"] == (1 if sort else 0)
+            assert ((out["hit"] & 15) != 0).sum() == (one["pclass"] != 0).sum()
+            _check_intervals(out["stats"])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", [39, 101, 127])
 def test_query_order_detection(n):
@@ -167,3 +216,6 @@ def test_query_order_detection(n):
     m = run_gpu(mmg)
     assert m["stats"]["sorted"] == 0
     np.testing.assert_array_equal(m["elem"], a["elem"][perm])
+    # the auto routes with a host read-back (n = 101, 127: auto -> input, auto -> Morton) record their events too
+    for out in (a, b, m):
+        _check_intervals(out["stats"])

@@ -21,7 +21,7 @@ from parmmg_amd.transfer import pack_solutions, pack_tet8
 SENT = np.frombuffer(np.uint64(0x7FF4A5A5A5A5A5A5).tobytes(), np.float64)[0]
 SENT_BITS = np.uint64(0x7FF4A5A5A5A5A5A5)
 
-# kLayouts of pmmg_hip.hip, assembled from the pool: (metric, fields)
+# kLayouts of pmmg_call.hpp, assembled from the pool: (metric, fields)
 POOL = {1: ("s0", "s1", "s2", "s3", "s4"), 3: ("vec",), 6: ("ten6",)}
 LAYOUTS = ((6, 1, 3, 6), (6, 1, 3, 6, 1), (1, 1), (1, 1, 1, 1, 1, 1), (1, 1, 1), (6,), (1,), (6, 1), (1, 1, 3, 6), ())
 RUNTIME = (3, 1, 6, 3)  # no compiled layout: the runtime variant, without a metric
@@ -64,7 +64,7 @@ def test_layout_list_is_the_kernels():
     """A layout added to kLayouts cannot go untested (CPU: no kernel runs).  packed_forms restates
     PackedLayout::valid() and passes_ok() and is held here to hand-worked cases only; a later change to either
     shows only through the GPU runs below: a layout that leaves the packed set is refused by set_solutions_packed."""
-    src = (Path(__file__).resolve().parents[1] / "parmmg_amd" / "csrc" / "pmmg_hip.hip").read_text()
+    src = (Path(__file__).resolve().parents[1] / "parmmg_amd" / "csrc" / "pmmg_call.hpp").read_text()
     table = src[src.index("const LayoutEntry kLayouts[]"):]
     table = table[:table.index("};")]
     got = [tuple(int(x) for x in m.groups() if int(x) > 0)

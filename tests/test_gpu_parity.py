@@ -24,7 +24,7 @@ CASES = {
 
 def _packable(case):
     """metric + fields of at most 16 doubles, no tensor across doubles 8/9, a
-    compiled layout (pick_layout in pmmg_hip.hip)"""
+    compiled layout (pick_layout in pmmg_call.hpp)"""
     sizes = ([case["met"].shape[1]] if case["met"] is not None else []) + [f.shape[1] for f in case["fields"]]
     return tuple(sizes) in {(6, 1, 3, 6), (1, 1), (1, 1, 1, 1, 1, 1), (1, 1, 1), (6,), (1,), (6, 1)}
 
