@@ -556,6 +556,85 @@ int pmmg_hip_metis_graph(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne,
                          int cap, int64_t *nadjncy,
                          int *xadj, int *adjncy, int *adjwgt);
 
+/* ---- Contiguity of a partition: the subgroups of a part, and their fix ------
+ * What the reference does with the same two inputs as the graph, the tetra
+ * adjacency and a colour per tetra, right after METIS:
+ * PMMG_check_part_contiguity (src/metis_pmmg.c:312), PMMG_check_grps_contiguity
+ * (:446, one colour: part == NULL) and PMMG_check_contiguity
+ * (src/moveinterfaces_pmmg.c:309) count the subgroups of every colour;
+ * PMMG_fix_contiguity (:475-523, through PMMG_fix_contiguity_centralized :577
+ * and PMMG_fix_contiguity_split :534) merges all but the largest subgroup of
+ * every colour into a neighbouring colour.  A subgroup is a connected
+ * component of the adjacency graph restricted to one colour.  Device pointers
+ * unless marked host, synchronous, main stream only.
+ *   tetra   from tet8 when non-NULL, else from adja; tetv may be NULL (every
+ *           row then counts as used); with tet8 == NULL && adja == NULL the
+ *           adjacency is built first from tetv (pmmg_hip_build_adjacency's
+ *           kernels, into context scratch, with that function's failures and
+ *           messages; np is taken as the largest vertex id).  A tetra with
+ *           v[0] <= 0 is unused: it belongs to no subgroup, its part is never
+ *           written and has no influence on any output.  The adjacency must be symmetric, as
+ *           MMG3D_hashTetra's is; this is not checked.
+ *   part[ne]        the colour of every tetra, in [0, ncolor); NULL: one
+ *                   colour for the whole mesh (ncolor must be 1).
+ * pmmg_hip_part_subgroups:
+ *   head[ne]        (may be NULL) the lowest tetra of the subgroup, 1-based; 0
+ *                   for an unused tetra
+ *   flag[ne]        (may be NULL) 1 + the number of subgroups of the same
+ *                   colour with a lower head: the value the reference's sweeps
+ *                   leave in flag (src/metis_pmmg.c:347, :486); 0 for an
+ *                   unused tetra
+ *   ncomp[ncolor]   (host) subgroups per colour
+ *   sub[cap], *nsub (host) the table in ascending head and its length;
+ *                   cap < *nsub returns 0 with *nsub, ncomp, head and flag
+ *                   filled and nothing written to sub (call with cap 0 to size)
+ *   *rounds         (host, may be NULL) hooking rounds of the labelling, at
+ *                   most 2 ceil(log2 ne) + 1 (2 for ne = 1)
+ * pmmg_hip_fix_contiguity: PMMG_fix_contiguity for colours 0 .. ncolor-1 (the
+ * centralized call's PMMG_set_color(igrp) == igrp).  For c ascending: the
+ * subgroups of colour c in the current part, in ascending head; main = the
+ * first; for every later one, next: if next.size > main.size, main takes the
+ * colour across its exit and next becomes main (main.exit == 0: nothing moves,
+ * main stays, *nstuck++); otherwise next takes the colour across its exit
+ * (next.exit == 0: *nstuck++).  The colour's changes are applied before colour
+ * c + 1 is looked at.  *nmerged counts the moved subgroups, *nmoved their
+ * tetra.
+ * Deviation: the reference moves a subgroup to the colour of the first foreign
+ * neighbour in BFS order from its head (list_otetra, :280-296), a property of
+ * a sequential traversal; this call takes the lowest (tetra, face) of the
+ * subgroup whose neighbour has another colour, the table's `exit`.  The two
+ * agree where a subgroup's head lies on its rim.
+ * Returns 0 (message in pmmg_hip_last_error) with nothing written to part, sub,
+ * head or flag when a link lies outside [4, 4*ne+3] or points to an unused
+ * tetra, a used tetra's part lies outside [0, ncolor), part == NULL with
+ * ncolor != 1, or ne >= 2^29.  tet8 / tetv / adja 16-byte, part / head / flag
+ * 4-byte aligned.  Labels and the table live in the context
+ * (pmmg_hip_release_scratch).  Two calls on the same inputs give
+ * byte-identical outputs. */
+typedef struct {
+  int color;  /* the part the subgroup belongs to */
+  int head;   /* its lowest tetra, 1-based: where the reference's scan opens its list */
+  int size;   /* tetra in it */
+  int exit;   /* 4*k+f (k 1-based) of the lowest (tetra, face) of the subgroup whose
+                 neighbour has another colour; 0: it touches no other colour */
+} pmmg_hip_subgroup;
+
+int pmmg_hip_part_subgroups(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *adja,
+                            const int *tet8, const int *part, int ncolor,
+                            int *head, int *flag,
+                            int *ncomp,
+                            int cap, pmmg_hip_subgroup *sub, int64_t *nsub,
+                            int *rounds);
+
+int pmmg_hip_fix_contiguity(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *adja,
+                            const int *tet8, int *part, int ncolor,
+                            int64_t *nmoved, int *nmerged, int *nstuck);
+
+/* Diagnostic, not part of the reference's interface: flatten passes of the
+ * context's last contiguity call (reported by tools/contiguity_time.py); -1
+ * without a context. */
+int64_t pmmg_hip_contig_passes(pmmg_hip_ctx *ctx);
+
 /* ---- One group split over the GPUs of a node -------------
  * One process per GPU (ParMmg's MPI ranks; GPU = node-local rank,
  * src/parmmg.c:121).  Each rank transfers its part of the group's new points

@@ -67,6 +67,12 @@ class HipLenHisto(ctypes.Structure):
         return d
 
 
+class HipSubgroup(ctypes.Structure):
+    """``pmmg_hip_subgroup`` of include/parmmg_hip.h."""
+
+    _fields_ = [("color", c_int), ("head", c_int), ("size", c_int), ("exit", c_int)]
+
+
 class HipGroup(ctypes.Structure):
     """``pmmg_hip_group`` of include/parmmg_hip.h (device pointers)."""
 
@@ -120,6 +126,11 @@ HIP_API = {
     "pmmg_hip_mesh_stats_bytes": (c_int64, [c_void_p]),
     "pmmg_hip_metis_graph": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                      c_int, P(c_int64), c_void_p, c_void_p, c_void_p]),
+    "pmmg_hip_part_subgroups": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                        P(c_int), c_int, P(HipSubgroup), P(c_int64), P(c_int)]),
+    "pmmg_hip_fix_contiguity": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, P(c_int64),
+                                        P(c_int), P(c_int)]),
+    "pmmg_hip_contig_passes": (c_int64, [c_void_p]),
     "pmmg_hip_memcpy_h2d": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "pmmg_hip_memcpy_d2h": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "pmmg_hip_locate_interp_rec": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -194,6 +205,8 @@ HOST_API = {
     "pmmg_graph_mesh_elts2metis": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                            P(P(c_int)), P(P(c_int)), P(P(c_int)), P(c_int64)]),
     "pmmg_host_free": (None, [c_void_p]),
+    "pmmg_check_part_contiguity": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "pmmg_fix_contiguity_split": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "pmmg_max_tet_extent": (c_double, [c_int, c_void_p, c_int, c_void_p]),
     "pmmg_shard_mark": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                                 c_void_p, P(c_int64)]),

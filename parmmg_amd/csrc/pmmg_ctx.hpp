@@ -23,6 +23,7 @@
 #include "pmmg_snapshot.hpp"
 #include "pmmg_meshstats.hpp"
 #include "pmmg_graph.hpp"
+#include "pmmg_contig.hpp"
 
 using namespace pmmg;
 
@@ -60,6 +61,7 @@ struct CtxBufs {
   SnapCache snap_cache; // the snapshot kernels' scratch (pmmg_snapshot.hip)
   StatsCache stats_cache; // pmmg_hip_qual_histo / pmmg_hip_edge_lengths: edge table, slabs (pmmg_meshstats.hip)
   GraphCache graph_cache; // pmmg_hip_metis_graph: block counts, scan scratch, a built adjacency (pmmg_graph.hip)
+  ContigCache contig_cache; // pmmg_hip_part_subgroups / pmmg_hip_fix_contiguity: labels, the table (pmmg_contig.hip)
   struct Kept { // a carry-over slot (see pmmg_hip_ctx::carry_slot)
     DevBuf xyz, met;
     std::vector<DevBuf> f;

@@ -592,6 +592,7 @@ int pmmg_hip_release_scratch(pmmg_hip_ctx *c) {
   c->snap_cache = SnapCache{};
   c->stats_cache = StatsCache{};
   c->graph_cache = GraphCache{};
+  c->contig_cache = ContigCache{};
   for (DevBuf *b : {&c->bvals2, &c->rs_hist, &c->rs_csum, &c->start_tab}) b->release();
   c->start_valid = false; // (the next call with a point map builds the start tables again)
   for (pmmg_hip_ctx *l : c->lanes) pmmg_hip_destroy(l);
@@ -767,6 +768,62 @@ int pmmg_hip_metis_graph(pmmg_hip_ctx *c, int np, const double *xyz, int ne, con
   return pmmg_graph_metis(c->stream, np, xyz, ne, t0, packed ? 2 : 1, a0, packed ? 2 : 1, wgt ? 1 : 0, met_size, met,
                           cap, nadjncy, xadj, adjncy, adjwgt, &c->graph_cache, &c->snap_cache, c->err, sizeof(c->err));
 }
+
+// ---- contiguity of a partition (pmmg_contig.hip)
+
+// the arguments the two contiguity calls share; fills *m
+static int contig_args(pmmg_hip_ctx *c, const char *who, int ne, const int *tetv, const int *adja, const int *tet8,
+                       const int *part, int ncolor, ContigMesh *m) {
+  const bool packed = tet8 != nullptr;
+  if (ne < 0 || ncolor < 1 || (ne > 0 && !packed && !tetv && !adja)) {
+    set_err(c, "%s: invalid arguments (ne=%d ncolor=%d)", who, ne, ncolor);
+    return 0;
+  }
+  if (!part && ncolor != 1) {
+    set_err(c, "%s: part == NULL is one colour for the whole mesh: ncolor = %d must be 1", who, ncolor);
+    return 0;
+  }
+  if (ne >= (1 << 29)) {
+    set_err(c, "%s: %d tetra exceed the 4*k+i adjacency encoding (2^29)", who, ne);
+    return 0;
+  }
+  const int *t0 = packed ? tet8 : tetv, *a0 = packed ? tet8 + 4 : adja;
+  if (ne > 0 && (!aligned16(t0) || !aligned16(a0) || ((uintptr_t)part & 3))) {
+    set_err(c, "%s: device tetra arrays must be 16-byte, part 4-byte aligned", who);
+    return 0;
+  }
+  *m = ContigMesh{ne, t0, packed ? 2 : 1, a0, packed ? 2 : 1};
+  return 1;
+}
+
+int pmmg_hip_part_subgroups(pmmg_hip_ctx *c, int ne, const int *tetv, const int *adja, const int *tet8,
+                            const int *part, int ncolor, int *head, int *flag, int *ncomp, int cap,
+                            pmmg_hip_subgroup *sub, int64_t *nsub, int *rounds) {
+  if (!enter(c)) return 0;
+  ContigMesh m;
+  if (!contig_args(c, "part_subgroups", ne, tetv, adja, tet8, part, ncolor, &m)) return 0;
+  if (!ncomp || !nsub || cap < 0 || (cap > 0 && !sub) || ((uintptr_t)head & 3) || ((uintptr_t)flag & 3)) {
+    set_err(c, "part_subgroups: invalid arguments (cap=%d; head / flag must be 4-byte aligned)", cap);
+    return 0;
+  }
+  return pmmg_contig_subgroups(c->stream, m, part, ncolor, head, flag, ncomp, cap, sub, nsub, rounds,
+                               &c->contig_cache, &c->snap_cache, c->err, sizeof(c->err));
+}
+
+int pmmg_hip_fix_contiguity(pmmg_hip_ctx *c, int ne, const int *tetv, const int *adja, const int *tet8, int *part,
+                            int ncolor, int64_t *nmoved, int *nmerged, int *nstuck) {
+  if (!enter(c)) return 0;
+  ContigMesh m;
+  if (!contig_args(c, "fix_contiguity", ne, tetv, adja, tet8, part, ncolor, &m)) return 0;
+  if (!nmoved || !nmerged || !nstuck) {
+    set_err(c, "fix_contiguity: invalid arguments (a NULL counter)");
+    return 0;
+  }
+  return pmmg_contig_fix(c->stream, m, part, ncolor, nmoved, nmerged, nstuck, &c->contig_cache, &c->snap_cache,
+                         c->err, sizeof(c->err));
+}
+
+int64_t pmmg_hip_contig_passes(pmmg_hip_ctx *c) { return c ? c->contig_cache.passes : -1; }
 
 int pmmg_hip_build_boundary(pmmg_hip_ctx *c, int np, int ne, const int *tet8, const int *tetv, const int *adja,
                             const int *tref, int cap, int *nt, int *triv, int *adjt) {

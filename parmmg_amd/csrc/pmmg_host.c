@@ -318,3 +318,75 @@ int pmmg_graph_mesh_elts2metis(pmmg_hip_ctx *ctx, int np, const double *xyz, int
   *nadjncy = n;
   return 1;
 }
+
+/* ---------------------------------------------------------------- contiguity of a partition */
+
+/* the host arrays that are given (each may be NULL), on the device: d[0] tetv, d[1] adja, d[2] part */
+static int contig_up(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *adja, const int *part, void *d[3]) {
+  const void *src[3] = {tetv, adja, part};
+  const int64_t bytes[3] = {(int64_t)sizeof(int) * 4 * ne, (int64_t)sizeof(int) * 4 * ne, (int64_t)sizeof(int) * ne};
+  d[0] = d[1] = d[2] = NULL;
+  for (int i = 0; i < 3; i++) {
+    if (!src[i] || ne == 0) continue;
+    d[i] = pmmg_hip_malloc(ctx, bytes[i]);
+    if (!d[i] || !pmmg_hip_memcpy_h2d(ctx, d[i], src[i], bytes[i])) return 0;
+  }
+  return 1;
+}
+
+static void contig_free(pmmg_hip_ctx *ctx, void *d[3]) {
+  for (int i = 0; i < 3; i++)
+    if (d[i]) pmmg_hip_free(ctx, d[i]);
+}
+
+int pmmg_check_part_contiguity(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *adja, const int *part, int ncolor,
+                               int *ncomp) {
+  if (!ctx) {
+    fprintf(stderr, "[parmmg_host] no HIP context: the contiguity check has no CPU fallback\n");
+    return -1;
+  }
+  if (ne < 0 || ncolor < 1 || !ncomp || (ne > 0 && !tetv && !adja)) return -1;
+  void *d[3];
+  int64_t nsub = 0;
+  int ok = contig_up(ctx, ne, tetv, adja, part, d);
+  /* the table itself is not wanted, but a call without room for it returns 0: give it room, once more when the
+   * first guess was too small (the call then left *nsub, and only that refusal leaves it above cap) */
+  int64_t cap = ne < 4096 ? ne : 4096;
+  pmmg_hip_subgroup *sub = NULL;
+  for (int turn = 0; ok && turn < 2; turn++) {
+    sub = (pmmg_hip_subgroup *)malloc(sizeof(pmmg_hip_subgroup) * (size_t)(cap > 0 ? cap : 1));
+    if (!sub) {
+      ok = 0;
+      break;
+    }
+    nsub = 0;
+    ok = pmmg_hip_part_subgroups(ctx, ne, (const int *)d[0], (const int *)d[1], NULL, (const int *)d[2], ncolor, NULL,
+                                 NULL, ncomp, (int)cap, sub, &nsub, NULL);
+    free(sub);
+    if (ok || turn == 1 || nsub <= cap) break;
+    cap = nsub;
+    ok = 1;
+  }
+  contig_free(ctx, d);
+  return ok ? ncomp[ncolor - 1] : -1;
+}
+
+int pmmg_fix_contiguity_split(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *adja, int ngrp, int *part) {
+  if (!ctx) {
+    fprintf(stderr, "[parmmg_host] no HIP context: the contiguity fix has no CPU fallback\n");
+    return 0;
+  }
+  if (ne < 0 || ngrp < 1 || (ne > 0 && (!part || (!tetv && !adja)))) return 0;
+  if (ne == 0) return 1;
+  void *d[3];
+  int64_t nmoved = 0;
+  int nmerged = 0, nstuck = 0;
+  int ok = contig_up(ctx, ne, tetv, adja, part, d);
+  if (ok)
+    ok = pmmg_hip_fix_contiguity(ctx, ne, (const int *)d[0], (const int *)d[1], NULL, (int *)d[2], ngrp, &nmoved,
+                                 &nmerged, &nstuck);
+  if (ok && nmerged) ok = pmmg_hip_memcpy_d2h(ctx, part, d[2], (int64_t)sizeof(int) * ne);
+  contig_free(ctx, d);
+  return ok;
+}
+

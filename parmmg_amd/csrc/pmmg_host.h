@@ -134,6 +134,29 @@ int pmmg_graph_mesh_elts2metis(pmmg_hip_ctx *ctx, int np, const double *xyz, int
                                int64_t *nadjncy);
 void pmmg_host_free(void *p);
 
+/* ---- Contiguity of a partition ---------------------------------------------
+ * PMMG_check_part_contiguity (src/metis_pmmg.c:312) and, with part NULL,
+ * PMMG_check_grps_contiguity (:446) from host arrays in the "row r = entity
+ * r+1" layout, through pmmg_hip_part_subgroups: tetv[4*ne] (may be NULL when
+ * adja is given: every tetra is used), adja[4*ne] (NULL: built on the device
+ * from tetv), part[ne] with values in [0, ncolor) (NULL: one colour, ncolor
+ * must be 1).  ncomp[ncolor] receives the subgroup count of every colour, so
+ * that the caller can take the maximum.  Returns the reference's value, the
+ * count of the last colour (`return ncolors`, :391 / :528: the reference
+ * computes maxcolors and does not return it), or -1 on failure (the reason in
+ * pmmg_hip_last_error). */
+int pmmg_check_part_contiguity(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *adja, const int *part, int ncolor,
+                               int *ncomp);
+
+/* PMMG_fix_contiguity_split (src/moveinterfaces_pmmg.c:534) on host arrays,
+ * through pmmg_hip_fix_contiguity: part[ne] (in/out) holds the group of every
+ * tetra, in [0, ngrp).  The reference's split call colours group igrp by
+ * nprocs*igrp + myrank (PMMG_set_color) and this one by igrp: the colours are
+ * visited in the same order and the result, read as groups, is the same.  The
+ * choice of the neighbouring colour deviates from the reference as
+ * include/parmmg_hip.h describes.  Returns 1, or 0 with part unchanged. */
+int pmmg_fix_contiguity_split(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *adja, int ngrp, int *part);
+
 /* ---- halo shards of a background group (pmmg_shard.c) ----
  * All arrays in the "row r = entity r+1" layout of parmmg_hip.h. */
 

@@ -17,7 +17,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._native import HipGroup, HipLenHisto, HipQualHisto, HipStats, hip_lib, host_lib
+from ._native import HipGroup, HipLenHisto, HipQualHisto, HipStats, HipSubgroup, hip_lib, host_lib
 
 HOST, DEVICE = 0, 1
 PT_SKIP, PT_VOL, PT_BDY = 0, 1, 2
@@ -313,8 +313,8 @@ class TransferContext:
 
     def release_scratch(self) -> None:
         """pmmg_hip_release_scratch: free the snapshot buckets, the binning's
-        scratch, the reports' edge table, the element graph's scratch and the group lanes (re-allocated on
-        demand)."""
+        scratch, the reports' edge table, the element graph's and the contiguity calls' scratch and the group
+        lanes (re-allocated on demand)."""
         self._ck(self.lib.pmmg_hip_release_scratch(self.h), "release_scratch")
 
     def bytes_up(self, reset: bool = False) -> int:
@@ -434,6 +434,53 @@ class TransferContext:
                 if a is not None:
                     a.shape, a.nbytes = (n.value,), 4 * n.value
         return xadj, adjncy, (adjwgt if weights else None)
+
+    def part_subgroups(self, tetv, adja=None, tet8=None, part=None, ncolor=1, head=None, flag=None, cap=None):
+        """The subgroups (connected components of the adjacency restricted to
+        one colour) of a partition on the device (pmmg_hip_part_subgroups):
+        device arrays.  Tetra from tet8 when given, else from adja; tetv may
+        be None when adja is given; with neither adja nor tet8 the adjacency is
+        built on the device.  part [ne] in [0, ncolor), or None: one colour.
+        head / flag: int32 device arrays [ne] to fill, or None.  Returns
+        dict(ncomp [ncolor], sub [nsub, 4] = color, head, size, exit in
+        ascending head, rounds, passes); cap: rows of the table (None: one
+        call counts first)."""
+        given = [a for a in (tetv, adja, tet8, part, head, flag) if a is not None]
+        if not all(_is_dev(a) for a in given):
+            raise ValueError("part_subgroups takes device arrays")
+        ne = (tet8 if tet8 is not None else (adja if adja is not None else tetv)).shape[0]
+        ncomp = (ctypes.c_int * int(ncolor))()
+        n, rounds = ctypes.c_int64(0), ctypes.c_int(0)
+
+        def call(cap_, table):
+            return self.lib.pmmg_hip_part_subgroups(self.h, ne, _p(tetv), _p(adja), _p(tet8), _p(part), int(ncolor),
+                                                    _p(head), _p(flag), ncomp, int(cap_), table, ctypes.byref(n),
+                                                    ctypes.byref(rounds))
+
+        if cap is None:
+            if not call(0, None) and n.value == 0:
+                self._ck(0, "part_subgroups")
+            cap = n.value
+        table = (HipSubgroup * max(1, int(cap)))()
+        self._ck(call(cap, table), "part_subgroups")
+        sub = np.array([(r.color, r.head, r.size, r.exit) for r in table[:n.value]], np.int32).reshape(-1, 4)
+        return dict(ncomp=np.array(list(ncomp), np.int32), sub=sub, rounds=rounds.value,
+                    passes=int(self.lib.pmmg_hip_contig_passes(self.h)))
+
+    def fix_contiguity(self, tetv, part, ncolor, adja=None, tet8=None):
+        """PMMG_fix_contiguity for colours 0 .. ncolor-1 on the device
+        (pmmg_hip_fix_contiguity): part (device int32 [ne]) is changed in
+        place.  Returns dict(nmoved, nmerged, nstuck, passes)."""
+        given = [a for a in (tetv, adja, tet8, part) if a is not None]
+        if not all(_is_dev(a) for a in given):
+            raise ValueError("fix_contiguity takes device arrays")
+        ne = (tet8 if tet8 is not None else (adja if adja is not None else tetv)).shape[0]
+        nmoved, nmerged, nstuck = ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0)
+        self._ck(self.lib.pmmg_hip_fix_contiguity(self.h, ne, _p(tetv), _p(adja), _p(tet8), _p(part), int(ncolor),
+                                                  ctypes.byref(nmoved), ctypes.byref(nmerged), ctypes.byref(nstuck)),
+                 "fix_contiguity")
+        return dict(nmoved=nmoved.value, nmerged=nmerged.value, nstuck=nstuck.value,
+                    passes=int(self.lib.pmmg_hip_contig_passes(self.h)))
 
     # ------------------------------------------------------------------ split over GPUs (RCCL)
     @staticmethod
