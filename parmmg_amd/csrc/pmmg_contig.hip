@@ -63,12 +63,10 @@ constexpr int kCSlots = 1024;     // LDS size table of a block
 constexpr int kCProbe = 8;        // slots tried before a count goes to the global word directly
 constexpr int kCJumps = 16;       // parents followed per tetra and flatten pass
 
-// flag bits of a call
-enum { C_BADLINK = 1, C_BADPART = 2, C_UNUSED = 4, C_TOUNUSED = 8 };
+// the call's own flag bit, beside the MESH_ bits of pmmg_devutil.hpp
+enum { C_BADPART = 2 };
 // the call's words on the device
 enum { W_FLAGS = 0, W_PASS = 1, W_VMAX = 2, W_COUNT = 4 };
-
-__device__ __forceinline__ bool link_ok(int a, int ne) { return (unsigned int)(a - 4) <= 4u * (unsigned int)ne - 1u; }
 
 // Round 1 and the checks.  P[k] = -1 for an unused row, else the lowest same-colour neighbour below k, or k.
 // flags: a link out of range, a colour outside [0, ncolor), an unused row seen.
@@ -79,7 +77,7 @@ __global__ __launch_bounds__(kCBlock) void k_contig_init(int ne, const int4 *tet
   for (int k = (int)blockIdx.x * kCBlock + (int)threadIdx.x; k < ne; k += stride) {
     if (tetv && tetv[(size_t)k * tstride].x <= 0) {
       P[k] = -1;
-      bad |= C_UNUSED;
+      bad |= MESH_UNUSED;
       continue;
     }
     const int c = part ? part[k] : 0;
@@ -91,7 +89,7 @@ __global__ __launch_bounds__(kCBlock) void k_contig_init(int ne, const int4 *tet
     for (int f = 0; f < 4; f++) {
       if (!lk[f]) continue;
       if (!link_ok(lk[f], ne)) {
-        bad |= C_BADLINK;
+        bad |= MESH_BADLINK;
         continue;
       }
       const int nb = lk[f] / 4 - 1;
@@ -100,23 +98,6 @@ __global__ __launch_bounds__(kCBlock) void k_contig_init(int ne, const int4 *tet
     P[k] = lo;
   }
   if (bad) atomicOr(flags, bad);
-}
-
-// a mesh with unused rows: a link of a used row that points to an unused one.  Runs after k_contig_init found
-// every link in range.
-__global__ __launch_bounds__(kCBlock) void k_contig_links_used(int ne, const int4 *tetv, int tstride, const int4 *adja,
-                                                               int astride, int *flags) {
-  bool bad = false;
-  const int stride = (int)gridDim.x * kCBlock;
-  for (int k = (int)blockIdx.x * kCBlock + (int)threadIdx.x; k < ne; k += stride) {
-    if (tetv[(size_t)k * tstride].x <= 0) continue;
-    const int4 a = adja[(size_t)k * astride];
-    const int lk[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-    for (int f = 0; f < 4; f++)
-      if (lk[f] && tetv[(size_t)(lk[f] / 4 - 1) * tstride].x <= 0) bad = true;
-  }
-  if (bad) atomicOr(flags, (int)C_TOUNUSED);
 }
 
 // One hooking round on a flat forest: L[k] = P[k] = k's root.  L is only read; the hooks go to P, at roots, whose
@@ -174,32 +155,12 @@ __global__ __launch_bounds__(kCBlock) void k_contig_flatten(int ne, int jumps, i
   if (left) *unfinished = 1;
 }
 
-// the block's sum of c in *total and, in every thread, the sum over the threads before it
-__device__ __forceinline__ int block_prefix(int c, int *wt, int *total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = c;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wt[w] = x;
-  __syncthreads();
-  int pos = x - c, t = 0;
-  for (int i = 0; i < kCWaves; i++) {
-    if (i < w) pos += wt[i];
-    t += wt[i];
-  }
-  *total = t;
-  return pos;
-}
-
 // heads (L[k] == k) of block b = tetra 256 b .. 256 b + 255
 __global__ __launch_bounds__(kCBlock) void k_contig_heads_count(int ne, const int *L, int *btot) {
   __shared__ int wt[kCWaves];
   const int k = (int)blockIdx.x * kCBlock + (int)threadIdx.x;
   const int c = (k < ne && L[k] == k) ? 1 : 0;
-  int n;
-  (void)block_prefix(c, wt, &n);
+  const int n = block_reduce<kCWaves>(c, wt, IntSum());
   if (threadIdx.x == 0) btot[blockIdx.x] = n;
 }
 
@@ -210,7 +171,7 @@ __global__ __launch_bounds__(kCBlock) void k_contig_heads_fill(int ne, const int
   const int k = (int)blockIdx.x * kCBlock + (int)threadIdx.x;
   const bool head = k < ne && L[k] == k;
   int n;
-  const int pos = boff[blockIdx.x] + block_prefix(head ? 1 : 0, wt, &n);
+  const int pos = boff[blockIdx.x] + block_prefix<kCWaves>(head ? 1 : 0, wt, &n);
   if (head) {
     idx[k] = pos;
     sub[pos] = ContigSub{part ? part[k] : 0, k + 1, 0, INT_MAX};
@@ -329,13 +290,8 @@ __global__ __launch_bounds__(kCBlock) void k_contig_vmax(int ne, const int4 *tet
     const int4 v = tetv[k];
     m = max(max(m, max(v.x, v.y)), max(v.z, v.w));
   }
-  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_down(m, o));
-  if ((threadIdx.x & 63) == 0) wt[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kCWaves; w++) m = max(m, wt[w]);
-    atomicMax(vmax, m);
-  }
+  m = block_reduce<kCWaves>(m, wt, IntMax());
+  if (threadIdx.x == 0) atomicMax(vmax, m);
 }
 
 int ceil_log2(int n) {
@@ -349,18 +305,11 @@ int grid_for(int ne) {
   return b < 1 ? 1 : (b > kCMaxBlocks ? kCMaxBlocks : b);
 }
 
-// a word of the call back on the host
-int read_word(hipStream_t s, const int *d, int *h, char *msg, size_t msglen) {
-  DEVCK(hipMemcpyAsync(h, d, sizeof(int), hipMemcpyDeviceToHost, s));
-  DEVCK(hipStreamSynchronize(s));
-  return 1;
-}
-
-// the link rows of a call that came without any, built into the cache
-int ensure_adja(hipStream_t s, ContigMesh *m, ContigCache *c, SnapCache *snap, char *msg, size_t msglen) {
+// the link rows of a call that came without any, built into the cache; np = the largest vertex id
+int ensure_adja(hipStream_t s, TetView *m, ContigCache *c, SnapCache *snap, char *msg, size_t msglen) {
   if (m->adja || m->ne == 0) return 1;
-  int *words = get<int>(c->words, W_COUNT), *built = get<int>(c->adja, 4 * (size_t)m->ne);
-  if (!words || !built) {
+  int *words = get<int>(c->words, W_COUNT);
+  if (!words) {
     snprintf(msg, msglen, "contiguity: out of device memory (adjacency of %d tetra)", m->ne);
     return 0;
   }
@@ -374,17 +323,14 @@ int ensure_adja(hipStream_t s, ContigMesh *m, ContigCache *c, SnapCache *snap, c
     snprintf(msg, msglen, "build_adjacency: vertex ids out of [1, np] or repeated in a tetra");
     return 0;
   }
-  if (!pmmg_snap_adjacency(s, np, m->ne, m->tetv, built, nullptr, snap, msg, msglen)) return 0;
-  m->adja = built;
-  m->astride = 1;
-  return 1;
+  return built_adjacency(s, "contiguity", np, m, c->adja, snap, msg, msglen);
 }
 
 // L of the current colours.  fresh: from singletons, with the call's refusals (the checks of k_contig_init);
 // else from L and P of the last labelling, after whole subgroups of it took another colour: each still
 // carries its own lowest tetra, a valid root in the colour it joined, and only the joins remain to be
 // hooked.  *rounds: hooking rounds, the fused first one and the idle last one included.
-int label(hipStream_t s, const ContigMesh &m, const int *part, int ncolor, bool fresh, ContigCache *c, int *rounds,
+int label(hipStream_t s, const TetView &m, const int *part, int ncolor, bool fresh, ContigCache *c, int *rounds,
           char *msg, size_t msglen) {
   const int ne = m.ne, grid = grid_for(ne);
   int *L = get<int>(c->label, (size_t)ne), *P = get<int>(c->parent, (size_t)ne), *words = get<int>(c->words, W_COUNT);
@@ -400,7 +346,7 @@ int label(hipStream_t s, const ContigMesh &m, const int *part, int ncolor, bool 
     DEVCK(hipGetLastError());
     int f = 0;
     if (!read_word(s, words + W_FLAGS, &f, msg, msglen)) return 0;
-    if (f & C_BADLINK) {
+    if (f & MESH_BADLINK) {
       snprintf(msg, msglen, "contiguity: an adja entry lies outside [4, 4*%d+3] (nothing written)", ne);
       return 0;
     }
@@ -408,16 +354,7 @@ int label(hipStream_t s, const ContigMesh &m, const int *part, int ncolor, bool 
       snprintf(msg, msglen, "contiguity: a used tetra has a part value outside [0, %d) (nothing written)", ncolor);
       return 0;
     }
-    if (f & C_UNUSED) {
-      hipLaunchKernelGGL(k_contig_links_used, dim3(grid), dim3(kCBlock), 0, s, ne, tv, m.tstride, av, m.astride,
-                         words + W_FLAGS);
-      DEVCK(hipGetLastError());
-      if (!read_word(s, words + W_FLAGS, &f, msg, msglen)) return 0;
-      if (f & C_TOUNUSED) {
-        snprintf(msg, msglen, "contiguity: an adja entry points to an unused tetra (nothing written)");
-        return 0;
-      }
-    }
+    if (!check_links<kCBlock>(s, "contiguity", " (nothing written)", m, words + W_FLAGS, &f, msg, msglen)) return 0;
   }
   const int cap = 2 * ceil_log2(ne > 2 ? ne : 2) + 1; // of the hooking rounds: the bound of the file's header
   const int pass_cap = ceil_log2(ne) + 2;             // of a round's flatten passes (17-fold each: ceil(log17 ne) + 1)
@@ -455,24 +392,20 @@ int label(hipStream_t s, const ContigMesh &m, const int *part, int ncolor, bool 
 }
 
 // the table of the labelled forest, on the device (cache->sub, ->exitcol, ->idx) and on the host
-int table(hipStream_t s, const ContigMesh &m, const int *part, ContigCache *c, std::vector<ContigSub> *T,
+int table(hipStream_t s, const TetView &m, const int *part, ContigCache *c, std::vector<ContigSub> *T,
           std::vector<int> *exitcol, char *msg, size_t msglen) {
   const int ne = m.ne, nblk = (ne + kCBlock - 1) / kCBlock;
   const int *L = c->label.as<int>();
+  char oom[96];
+  snprintf(oom, sizeof(oom), "contiguity: out of device memory (table index of %d tetra)", ne);
   int *idx = get<int>(c->idx, (size_t)ne);
-  int *btot = get<int>(c->btot, (size_t)nblk + 1), *boff = get<int>(c->boff, (size_t)nblk + 1);
-  if (!idx || !btot || !boff) {
-    snprintf(msg, msglen, "contiguity: out of device memory (table index of %d tetra)", ne);
-    return 0;
-  }
-  size_t tb = 0;
-  if (!scan_reserve(c->scan, btot, boff, nblk + 1, s, &tb, msg, msglen)) return 0;
-  DEVCK(hipMemsetAsync(btot + nblk, 0, sizeof(int), s));
-  hipLaunchKernelGGL(k_contig_heads_count, dim3(nblk), dim3(kCBlock), 0, s, ne, L, btot);
+  if (!idx) return refuse(msg, msglen, oom);
+  if (!reserve(c->heads, nblk, s, oom, msg, msglen)) return 0;
+  const int *boff = c->heads.boff.as<int>();
+  hipLaunchKernelGGL(k_contig_heads_count, dim3(nblk), dim3(kCBlock), 0, s, ne, L, c->heads.btot.as<int>());
   DEVCK(hipGetLastError());
-  if (!exclusive_scan(c->scan, btot, boff, nblk + 1, s, msg, msglen)) return 0;
   int nsub = 0;
-  if (!read_word(s, boff + nblk, &nsub, msg, msglen)) return 0;
+  if (!offsets(c->heads, s, nblk, &nsub, msg, msglen)) return 0;
   T->assign((size_t)nsub, ContigSub{0, 0, 0, 0});
   exitcol->assign((size_t)nsub, -1);
   if (nsub == 0) return 1;
@@ -501,7 +434,7 @@ void count_colours(const std::vector<ContigSub> &T, int ncolor, int *ncomp) {
 
 } // namespace
 
-int pmmg_contig_subgroups(hipStream_t s, ContigMesh m, const int *part, int ncolor, int *head, int *flag, int *ncomp,
+int pmmg_contig_subgroups(hipStream_t s, TetView m, const int *part, int ncolor, int *head, int *flag, int *ncomp,
                           int cap, pmmg_hip_subgroup *sub, int64_t *nsub, int *rounds, ContigCache *cache,
                           SnapCache *snap, char *msg, size_t msglen) {
   *nsub = 0;
@@ -541,7 +474,7 @@ int pmmg_contig_subgroups(hipStream_t s, ContigMesh m, const int *part, int ncol
   return 1;
 }
 
-int pmmg_contig_fix(hipStream_t s, ContigMesh m, int *part, int ncolor, int64_t *nmoved, int *nmerged, int *nstuck,
+int pmmg_contig_fix(hipStream_t s, TetView m, int *part, int ncolor, int64_t *nmoved, int *nmerged, int *nstuck,
                     ContigCache *cache, SnapCache *snap, char *msg, size_t msglen) {
   *nmoved = 0;
   *nmerged = *nstuck = 0;

@@ -72,3 +72,10 @@ template <class T>
 T *get(DevBuf &b, size_t count) {
   return b.ensure(count * sizeof(T)) == hipSuccess ? static_cast<T *>(b.p) : nullptr;
 }
+
+// The counts of a count / fill kernel pair: btot[b] of block b, boff[b] the
+// sum before it, boff[nblk] the total; tmp is the scan's temporary
+// (reserve() and offsets() of pmmg_devutil.hpp).
+struct BlockScan {
+  DevBuf btot, boff, tmp;
+};

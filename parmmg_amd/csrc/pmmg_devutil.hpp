@@ -1,7 +1,9 @@
-// pmmg_devutil.hpp — what the host sides of pmmg_snapshot.hip,
-// pmmg_meshstats.hip and pmmg_graph.hip share: the error macro of a function
-// that reports through (msg, msglen) and returns 0, and the exclusive scan of
-// an int array with its temporary in a DevBuf.
+// pmmg_devutil.hpp — what the mesh services (pmmg_snapshot.hip, pmmg_meshstats.hip, pmmg_graph.hip,
+// pmmg_contig.hip) share.  Device side: the prefix and the reduction of one int per thread over a block,
+// the range check of a link, the flag bits of a pass over the links, the kernel that looks for a link to
+// an unused row.  Host side: the error macro of a function that reports through (msg, msglen) and returns
+// 0, a word read back, the exclusive scan of an int array, the two operations of a BlockScan, and the two
+// steps the graph and the contiguity calls share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -9,6 +11,75 @@
 #include <stdio.h>
 
 #include "pmmg_devbuf.hpp"
+#include "pmmg_snapshot.hpp"
+
+// ---------------------------------------------------------------- device side
+
+// The sum of c over the threads before this one and, in every thread, the block's sum in *total.  All
+// 64 * WAVES threads of the block call it; wt has WAVES ints.  No barrier after wt is read: a caller
+// that uses wt again synchronises first.  The sums are plain int additions, so a value that packs two
+// counters whose block sums stay in their fields ({flag << 16 | count}) is prefixed field by field.
+template <int WAVES>
+__device__ __forceinline__ int block_prefix(int c, int *wt, int *total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int x = c; // inclusive prefix within the wave
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(x, o);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) wt[w] = x;
+  __syncthreads();
+  int pos = x - c, t = 0;
+  for (int i = 0; i < WAVES; i++) {
+    if (i < w) pos += wt[i];
+    t += wt[i];
+  }
+  *total = t;
+  return pos;
+}
+
+struct IntSum { __device__ int operator()(int a, int b) const { return a + b; } };
+struct IntMax { __device__ int operator()(int a, int b) const { return a > b ? a : b; } };
+
+// op over the block's values of c, in thread 0 (the other threads get a partial).  Same contract as
+// block_prefix: all 64 * WAVES threads, wt of WAVES ints, no barrier at the end.
+template <int WAVES, class Op>
+__device__ __forceinline__ int block_reduce(int c, int *wt, Op op) {
+  for (int o = 32; o > 0; o >>= 1) c = op(c, __shfl_down(c, o));
+  if ((threadIdx.x & 63) == 0) wt[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < WAVES; w++) c = op(c, wt[w]);
+  return c;
+}
+
+// a link 4 k' + i' of a mesh of ne tetra lies in [4, 4 ne + 3]
+__device__ __forceinline__ bool link_ok(int a, int ne) { return (unsigned int)(a - 4) <= 4u * (unsigned int)ne - 1u; }
+
+// Flag bits of a pass over the links of a mesh.  Bit 2 is the pass's own (a vertex id, a colour).
+enum { MESH_BADLINK = 1, MESH_UNUSED = 4, MESH_TOUNUSED = 8 };
+
+// A mesh with unused rows (v[0] <= 0): a link of a used row that points to an unused one (the reference
+// requires a packed mesh).  Precondition: every non-zero link is in range (the pass that saw the unused
+// rows found no MESH_BADLINK).  Grid-stride: any grid is correct, and k + stride stays an int for ne < 2^29
+// and at most ceil(ne / BLOCK) blocks.  (A template, as check_links is: only a file that calls it has the kernel.)
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_links_to_unused(int ne, const int4 *tetv, int tstride, const int4 *adja,
+                                                           int astride, int *flags) {
+  bool bad = false;
+  const int stride = (int)gridDim.x * BLOCK;
+  for (int k = (int)blockIdx.x * BLOCK + (int)threadIdx.x; k < ne; k += stride) {
+    if (tetv[(size_t)k * tstride].x <= 0) continue;
+    const int4 a = adja[(size_t)k * astride];
+    const int lk[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int f = 0; f < 4; f++)
+      if (lk[f] && tetv[(size_t)(lk[f] / 4 - 1) * tstride].x <= 0) bad = true;
+  }
+  if (bad) atomicOr(flags, (int)MESH_TOUNUSED);
+}
+
+// ---------------------------------------------------------------- host side
 
 #define DEVCK(expr)                                                                                 \
   do {                                                                                              \
@@ -18,6 +89,19 @@
       return 0;                                                                                     \
     }                                                                                               \
   } while (0)
+
+// 0, with `text` in msg
+static inline int refuse(char *msg, size_t msglen, const char *text) {
+  snprintf(msg, msglen, "%s", text);
+  return 0;
+}
+
+// a word of the device back on the host; the stream is synchronised
+static inline int read_word(hipStream_t s, const int *d, int *h, char *msg, size_t msglen) {
+  DEVCK(hipMemcpyAsync(h, d, sizeof(int), hipMemcpyDeviceToHost, s));
+  DEVCK(hipStreamSynchronize(s));
+  return 1;
+}
 
 // The scan's temporary sized and tmp grown to it, nothing launched: for a
 // caller that wants the allocation (which may synchronise the device) ahead
@@ -37,5 +121,60 @@ static inline int exclusive_scan(DevBuf &tmp, const int *in, int *out, int n, hi
   size_t tb = 0;
   if (!scan_reserve(tmp, in, out, n, s, &tb, msg, msglen)) return 0;
   DEVCK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, in, out, n, s));
+  return 1;
+}
+
+// A BlockScan (pmmg_devbuf.hpp) ahead of its counting kernel: nblk + 1 entries of btot and boff and the
+// scan's temporary (an allocation may synchronise the device).  oom: the caller's message when the device
+// has no memory for the arrays.
+static inline int reserve(BlockScan &b, int nblk, hipStream_t s, const char *oom, char *msg, size_t msglen) {
+  const int *in = get<int>(b.btot, (size_t)nblk + 1);
+  int *out = get<int>(b.boff, (size_t)nblk + 1);
+  if (!in || !out) return refuse(msg, msglen, oom);
+  size_t tb = 0;
+  return scan_reserve(b.tmp, in, out, nblk + 1, s, &tb, msg, msglen);
+}
+
+// after the counting kernel: boff[b] = btot[0] + ... + btot[b - 1], b <= nblk, and with `total` the sum
+// boff[nblk] back on the host and the stream synchronised
+static inline int offsets(BlockScan &b, hipStream_t s, int nblk, int *total, char *msg, size_t msglen) {
+  int *in = b.btot.as<int>(), *out = b.boff.as<int>();
+  DEVCK(hipMemsetAsync(in + nblk, 0, sizeof(int), s));
+  if (!exclusive_scan(b.tmp, in, out, nblk + 1, s, msg, msglen)) return 0;
+  return total ? read_word(s, out + nblk, total, msg, msglen) : 1;
+}
+
+// The refusal of a mesh whose pass over the links left MESH_UNUSED in *h_flags (a copy of the device word
+// `flags`, no MESH_BADLINK in it): a link to an unused row.  *h_flags is read again after the kernel.
+// The message is "<who>: an adja entry points to an unused tetra<tail>".
+template <int BLOCK>
+int check_links(hipStream_t s, const char *who, const char *tail, const TetView &m, int *flags, int *h_flags,
+                char *msg, size_t msglen) {
+  if (!(*h_flags & MESH_UNUSED)) return 1;
+  const int nblk = (m.ne + BLOCK - 1) / BLOCK;
+  hipLaunchKernelGGL(k_links_to_unused<BLOCK>, dim3(nblk < 2048 ? nblk : 2048), dim3(BLOCK), 0, s, m.ne,
+                     reinterpret_cast<const int4 *>(m.tetv), m.tstride, reinterpret_cast<const int4 *>(m.adja),
+                     m.astride, flags);
+  DEVCK(hipGetLastError());
+  if (!read_word(s, flags, h_flags, msg, msglen)) return 0;
+  if (*h_flags & MESH_TOUNUSED) {
+    snprintf(msg, msglen, "%s: an adja entry points to an unused tetra%s", who, tail);
+    return 0;
+  }
+  return 1;
+}
+
+// The link rows of a call that came without any (m->adja NULL, m->tetv unpacked rows with ids in
+// [1, np]): built into `store` by pmmg_snap_adjacency, which sets msg when it refuses the mesh.
+static inline int built_adjacency(hipStream_t s, const char *who, int np, TetView *m, DevBuf &store, SnapCache *snap,
+                                  char *msg, size_t msglen) {
+  int *built = get<int>(store, 4 * (size_t)m->ne);
+  if (!built) {
+    snprintf(msg, msglen, "%s: out of device memory (adjacency of %d tetra)", who, m->ne);
+    return 0;
+  }
+  if (!pmmg_snap_adjacency(s, np, m->ne, m->tetv, built, nullptr, snap, msg, msglen)) return 0;
+  m->adja = built;
+  m->astride = 1;
   return 1;
 }

@@ -36,30 +36,8 @@ constexpr int kGBlock = 256;
 constexpr int kGWaves = kGBlock / 64;
 constexpr int kGEntries = 4 * kGBlock; // graph entries of a block at most
 
-// flag bits of a call
-enum { G_BADLINK = 1, G_BADID = 2, G_UNUSED = 4, G_TOUNUSED = 8 };
-
-// a link 4 k' + i' of a mesh of ne tetra lies in [4, 4 ne + 3]
-__device__ __forceinline__ bool link_ok(int a, int ne) { return (unsigned int)(a - 4) <= 4u * (unsigned int)ne - 1u; }
-
-// the block's sum of c in thread 0 and, in every thread, the sum over the threads before it
-__device__ __forceinline__ int block_prefix(int c, int *wt, int *total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = c; // inclusive prefix within the wave
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wt[w] = x;
-  __syncthreads();
-  int pos = x - c, t = 0;
-  for (int i = 0; i < kGWaves; i++) {
-    if (i < w) pos += wt[i];
-    t += wt[i];
-  }
-  *total = t;
-  return pos;
-}
+// the call's own flag bit, beside the MESH_ bits of pmmg_devutil.hpp
+enum { G_BADID = 2 };
 
 // Count pass.  btot[b]: graph entries of block b.  A used row (tetv NULL: every row) counts its non-zero
 // links; an unused one (v[0] <= 0) is an empty row whatever its links hold.  flags: a link out of range,
@@ -78,7 +56,7 @@ __global__ __launch_bounds__(kGBlock) void k_graph_count(int ne, const int4 *tet
       const int4 v = tetv[(size_t)k * tstride];
       used = v.x > 0;
       if (!used)
-        bad |= G_UNUSED;
+        bad |= MESH_UNUSED;
       else if (np_check && (v.x > np_check || v.y < 1 || v.y > np_check || v.z < 1 || v.z > np_check || v.w < 1 ||
                             v.w > np_check))
         bad |= G_BADID;
@@ -92,35 +70,16 @@ __global__ __launch_bounds__(kGBlock) void k_graph_count(int ne, const int4 *tet
           if (link_ok(lk[f], ne))
             c++;
           else
-            bad |= G_BADLINK;
+            bad |= MESH_BADLINK;
         }
     }
   }
   if (bad) atomicOr(&sflag, bad);
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-  if ((threadIdx.x & 63) == 0) wt[threadIdx.x >> 6] = c;
-  __syncthreads();
+  const int n = block_reduce<kGWaves>(c, wt, IntSum());
   if (threadIdx.x == 0) {
-    int s = 0;
-    for (int w = 0; w < kGWaves; w++) s += wt[w];
-    btot[blockIdx.x] = s;
+    btot[blockIdx.x] = n;
     if (sflag) atomicOr(flags, sflag);
   }
-}
-
-// a mesh with unused rows only: a link of a used row that points to an unused one (the reference requires
-// a packed mesh).  Runs after the count pass found every link in range.
-__global__ __launch_bounds__(kGBlock) void k_graph_links_used(int ne, const int4 *tetv, int tstride, const int4 *adja,
-                                                              int astride, int *flags) {
-  const long long k = (long long)blockIdx.x * kGBlock + threadIdx.x;
-  if (k >= ne || tetv[(size_t)k * tstride].x <= 0) return;
-  const int4 a = adja[(size_t)k * astride];
-  const int lk[4] = {a.x, a.y, a.z, a.w};
-  bool bad = false;
-#pragma unroll
-  for (int f = 0; f < 4; f++)
-    if (lk[f] && link_ok(lk[f], ne) && tetv[(size_t)(lk[f] / 4 - 1) * tstride].x <= 0) bad = true;
-  if (bad) atomicOr(flags, (int)G_TOUNUSED);
 }
 
 // words [lo, hi) of the block's LDS array to g, word j to g[j]; g is 16-byte aligned, so the whole quads
@@ -161,7 +120,7 @@ __global__ __launch_bounds__(kGBlock) void k_graph_fill(const double *xyz, int n
   const int lk[4] = {a.x, a.y, a.z, a.w};
   const int c = (a.x != 0) + (a.y != 0) + (a.z != 0) + (a.w != 0);
   int n;
-  const int pos = block_prefix(c, wt, &n);
+  const int pos = block_prefix<kGWaves>(c, wt, &n);
   const int base = boff[blockIdx.x];
   if (k < ne) xadj[k + 1] = base + pos + c;
   if (k == 0) xadj[0] = 0;
@@ -226,47 +185,34 @@ __global__ __launch_bounds__(kGBlock) void k_graph_fill(const double *xyz, int n
 
 } // namespace
 
-int pmmg_graph_metis(hipStream_t s, int np, const double *xyz, int ne, const int *tetv, int tstride, const int *adja,
-                     int astride, int want_wgt, int met_size, const double *met, int cap, int64_t *nadjncy, int *xadj,
-                     int *adjncy, int *adjwgt, GraphCache *cache, SnapCache *snap, char *msg, size_t msglen) {
+int pmmg_graph_metis(hipStream_t s, int np, const double *xyz, TetView m, int want_wgt, int met_size,
+                     const double *met, int cap, int64_t *nadjncy, int *xadj, int *adjncy, int *adjwgt,
+                     GraphCache *cache, SnapCache *snap, char *msg, size_t msglen) {
   *nadjncy = 0;
+  const int ne = m.ne;
   if (ne == 0) {
     DEVCK(hipMemsetAsync(xadj, 0, sizeof(int), s));
     DEVCK(hipStreamSynchronize(s));
     return 1;
   }
-  if (!adja) { // MMG3D_hashTetra's branch of src/metis_pmmg.c:756
-    int *built = get<int>(cache->adja, 4 * (size_t)ne);
-    if (!built) {
-      snprintf(msg, msglen, "metis_graph: out of device memory (adjacency of %d tetra)", ne);
-      return 0;
-    }
-    if (!pmmg_snap_adjacency(s, np, ne, tetv, built, nullptr, snap, msg, msglen)) return 0;
-    adja = built;
-    astride = 1;
-  }
-  const int4 *tv = reinterpret_cast<const int4 *>(tetv), *av = reinterpret_cast<const int4 *>(adja);
+  // MMG3D_hashTetra's branch of src/metis_pmmg.c:756
+  if (!m.adja && !built_adjacency(s, "metis_graph", np, &m, cache->adja, snap, msg, msglen)) return 0;
+  const int tstride = m.tstride, astride = m.astride;
+  const int4 *tv = reinterpret_cast<const int4 *>(m.tetv), *av = reinterpret_cast<const int4 *>(m.adja);
   const int nblk = (ne + kGBlock - 1) / kGBlock;
-  int *btot = get<int>(cache->btot, (size_t)nblk + 1), *boff = get<int>(cache->boff, (size_t)nblk + 1);
+  const char *oom = "metis_graph: out of device memory (block counts)";
   int *flags = get<int>(cache->flags, 4);
-  if (!btot || !boff || !flags) {
-    snprintf(msg, msglen, "metis_graph: out of device memory (block counts)");
-    return 0;
-  }
-  size_t tb = 0; // (the scan's temporary is allocated here, ahead of the count kernel)
-  if (!scan_reserve(cache->scan, btot, boff, nblk + 1, s, &tb, msg, msglen)) return 0;
-  // count, scan (one entry more than blocks: boff[nblk] is the total)
+  if (!flags) return refuse(msg, msglen, oom);
+  if (!reserve(cache->rows, nblk, s, oom, msg, msglen)) return 0; // (ahead of the count kernel)
+  int *btot = cache->rows.btot.as<int>(), *boff = cache->rows.boff.as<int>();
   DEVCK(hipMemsetAsync(flags, 0, 4 * sizeof(int), s));
-  DEVCK(hipMemsetAsync(btot + nblk, 0, sizeof(int), s));
   hipLaunchKernelGGL(k_graph_count, dim3(nblk), dim3(kGBlock), 0, s, ne, tv, tstride, av, astride, want_wgt ? np : 0,
                      btot, flags);
   DEVCK(hipGetLastError());
-  if (!exclusive_scan(cache->scan, btot, boff, nblk + 1, s, msg, msglen)) return 0;
   int h_flags = 0, h_total = 0;
-  DEVCK(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, s));
-  DEVCK(hipMemcpyAsync(&h_total, boff + nblk, sizeof(int), hipMemcpyDeviceToHost, s));
-  DEVCK(hipStreamSynchronize(s));
-  if (h_flags & G_BADLINK) {
+  DEVCK(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, s)); // (back with the total)
+  if (!offsets(cache->rows, s, nblk, &h_total, msg, msglen)) return 0;
+  if (h_flags & MESH_BADLINK) {
     snprintf(msg, msglen, "metis_graph: an adja entry lies outside [4, 4*%d+3] (nothing written to the lists)", ne);
     return 0;
   }
@@ -275,23 +221,14 @@ int pmmg_graph_metis(hipStream_t s, int np, const double *xyz, int ne, const int
              np);
     return 0;
   }
-  if (h_flags & G_UNUSED) {
-    hipLaunchKernelGGL(k_graph_links_used, dim3(nblk), dim3(kGBlock), 0, s, ne, tv, tstride, av, astride, flags);
-    DEVCK(hipGetLastError());
-    DEVCK(hipMemcpyAsync(&h_flags, flags, sizeof(int), hipMemcpyDeviceToHost, s));
-    DEVCK(hipStreamSynchronize(s));
-    if (h_flags & G_TOUNUSED) {
-      snprintf(msg, msglen, "metis_graph: an adja entry points to an unused tetra: the mesh must be packed (nothing "
-                            "written to the lists)");
-      return 0;
-    }
-  }
+  const char *tail = ": the mesh must be packed (nothing written to the lists)";
+  if (!check_links<kGBlock>(s, "metis_graph", tail, m, flags, &h_flags, msg, msglen)) return 0;
   *nadjncy = h_total;
   const bool lists = h_total <= cap;
   int *oa = lists ? adjncy : nullptr;
   const int mode = !want_wgt ? W_NONE : (met_size == 1 ? W_ISO : (met_size == 6 ? W_ANI : W_HUGE));
   // without weights the rows' vertices are read only where the count pass saw an unused row
-  const int4 *tf = (mode != W_NONE || (h_flags & G_UNUSED)) ? tv : nullptr;
+  const int4 *tf = (mode != W_NONE || (h_flags & MESH_UNUSED)) ? tv : nullptr;
 #define FILL(M)                                                                                              \
   hipLaunchKernelGGL(k_graph_fill<M>, dim3(nblk), dim3(kGBlock), 0, s, xyz, ne, tf, tstride, av, astride, met, boff, \
                      xadj, oa, adjwgt)

@@ -11,17 +11,16 @@
 // Device scratch of the graph passes, owned by a context and kept between
 // calls (grown, never shrunk).
 struct GraphCache {
-  DevBuf btot, boff, scan; // per-block counts, their offsets, the scan's temporary
-  DevBuf flags;            // the call's flag bits
-  DevBuf adja;             // the adjacency of a call that came without one
+  BlockScan rows; // graph entries per block, their offsets
+  DevBuf flags;   // the call's flag bits
+  DevBuf adja;    // the adjacency of a call that came without one
 };
 
-// pmmg_hip_metis_graph on checked arguments.  Tetra rows are int4 rows
-// `tstride` / `astride` int4s apart (1: separate arrays, 2: tet8); tetv may be
-// NULL without weights (every row counts as used); adja NULL: built from tetv
-// into the cache (pmmg_snap_adjacency, which sets msg when it fails).
+// pmmg_hip_metis_graph on checked arguments.  m.tetv may be NULL without
+// weights (every row counts as used); m.adja NULL: built from tetv into the
+// cache (pmmg_snap_adjacency, which sets msg when it fails).
 // want_wgt 0: adjwgt, xyz and met are not touched.  *nadjncy on the host.
 // Synchronous.  Returns 1, or 0 with msg set.
-int pmmg_graph_metis(hipStream_t s, int np, const double *xyz, int ne, const int *tetv, int tstride, const int *adja,
-                     int astride, int want_wgt, int met_size, const double *met, int cap, int64_t *nadjncy, int *xadj,
-                     int *adjncy, int *adjwgt, GraphCache *cache, SnapCache *snap, char *msg, size_t msglen);
+int pmmg_graph_metis(hipStream_t s, int np, const double *xyz, TetView m, int want_wgt, int met_size,
+                     const double *met, int cap, int64_t *nadjncy, int *xadj, int *adjncy, int *adjwgt,
+                     GraphCache *cache, SnapCache *snap, char *msg, size_t msglen);

@@ -100,14 +100,14 @@ static int set_background_impl(pmmg_hip_ctx *c, int np, const double *xyz, int n
     set_err(c, "set_background: invalid arguments (np=%d ne=%d nt=%d)", np, ne, nt);
     return 0;
   }
-  if (ne >= (1 << 29)) {
+  if (ne >= kTetMax) {
     set_err(c, "set_background: %d tetra exceed the 4*k+i adjacency encoding (2^29)", ne);
     return 0;
   }
   const bool dev = where == PMMG_HIP_DEVICE;
   if (dev) {
     const void *t0 = packed ? (const void *)tet8 : (const void *)tetv;
-    if (((uintptr_t)t0 & 15) || (!packed && adja && ((uintptr_t)adja & 15))) {
+    if (!aligned<16>(t0) || (!packed && !aligned<16>(adja))) {
       set_err(c, "set_background: device tetra arrays must be 16-byte aligned");
       return 0;
     }
@@ -163,15 +163,16 @@ static int set_background_impl(pmmg_hip_ctx *c, int np, const double *xyz, int n
       return 0;
     }
     if (build_bdy) {
-      const int *t0 = reinterpret_cast<const int *>(c->bg.tetv), *a0 = reinterpret_cast<const int *>(c->bg.adja);
+      const TetView m{ne, reinterpret_cast<const int *>(c->bg.tetv), c->bg.tstride,
+                      reinterpret_cast<const int *>(c->bg.adja), c->bg.tstride};
       int cnt = 0, ntb = 0;
       char msg[256];
-      pmmg_snap_boundary(c->stream, np, ne, t0, c->bg.tstride, a0, c->bg.tstride, nullptr, 0, &cnt, nullptr, nullptr,
-                         &c->snap_cache, msg, sizeof(msg)); // counts (fails on capacity 0 when there are trias)
+      pmmg_snap_boundary(c->stream, np, m, nullptr, 0, &cnt, nullptr, nullptr, &c->snap_cache, msg,
+                         sizeof(msg)); // counts (fails on capacity 0 when there are trias)
       if (!ensure(c, c->o_triv, sizeof(int) * 3 * (size_t)cnt) || !ensure(c, c->o_adjt, sizeof(int) * 3 * (size_t)cnt))
         return 0;
-      if (!pmmg_snap_boundary(c->stream, np, ne, t0, c->bg.tstride, a0, c->bg.tstride, nullptr, cnt, &ntb,
-                              c->o_triv.as<int>(), c->o_adjt.as<int>(), &c->snap_cache, c->err, sizeof(c->err))) {
+      if (!pmmg_snap_boundary(c->stream, np, m, nullptr, cnt, &ntb, c->o_triv.as<int>(), c->o_adjt.as<int>(),
+                              &c->snap_cache, c->err, sizeof(c->err))) {
         fprintf(stderr, "[parmmg_hip] %s\n", c->err);
         return 0;
       }
@@ -614,19 +615,17 @@ int pmmg_hip_locate_interp_groups(pmmg_hip_ctx *c, int ngroup, const pmmg_hip_gr
 
 // ---- background snapshot (pmmg_snapshot.hip)
 
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 int pmmg_hip_build_adjacency(pmmg_hip_ctx *c, int np, int ne, const int *tetv, int *adja, int *tet8) {
   if (!enter(c)) return 0;
   if (np <= 0 || ne <= 0 || !tetv || (!adja && !tet8)) {
     set_err(c, "build_adjacency: invalid arguments (np=%d ne=%d)", np, ne);
     return 0;
   }
-  if (ne >= (1 << 29)) {
+  if (ne >= kTetMax) {
     set_err(c, "build_adjacency: %d tetra exceed the 4*k+i adjacency encoding (2^29)", ne);
     return 0;
   }
-  if (!aligned16(tetv) || (adja && !aligned16(adja)) || (tet8 && !aligned16(tet8))) {
+  if (!aligned<16>(tetv) || (adja && !aligned<16>(adja)) || (tet8 && !aligned<16>(tet8))) {
     set_err(c, "build_adjacency: device arrays must be 16-byte aligned");
     return 0;
   }
@@ -641,7 +640,7 @@ int pmmg_hip_tetra_qual(pmmg_hip_ctx *c, int np, const double *xyz, int ne, cons
     set_err(c, "tetra_qual: invalid arguments (np=%d ne=%d met_size=%d)", np, ne, met_size);
     return 0;
   }
-  if (ne > 0 && !aligned16(tetv)) {
+  if (ne > 0 && !aligned<16>(tetv)) {
     set_err(c, "tetra_qual: tetv must be 16-byte aligned");
     return 0;
   }
@@ -669,7 +668,7 @@ int pmmg_hip_qual_histo(pmmg_hip_ctx *c, int ne, const int *tetv, const double *
     set_err(c, "qual_histo: invalid arguments (ne=%d)", ne);
     return 0;
   }
-  if (ne > 0 && !aligned16(tetv)) {
+  if (ne > 0 && !aligned<16>(tetv)) {
     set_err(c, "qual_histo: tetv must be 16-byte aligned");
     return 0;
   }
@@ -689,7 +688,7 @@ int pmmg_hip_edge_lengths(pmmg_hip_ctx *c, int np, const double *xyz, int ne, co
     set_err(c, "edge_lengths: invalid arguments (np=%d ne=%d nskip=%d cap=%d)", np, ne, nskip, cap);
     return 0;
   }
-  if ((ne > 0 && !aligned16(tetv)) || ((uintptr_t)skip & 7) || ((uintptr_t)edge_out & 7) || ((uintptr_t)len_out & 7)) {
+  if ((ne > 0 && !aligned<16>(tetv)) || !aligned<8>(skip) || !aligned<8>(edge_out) || !aligned<8>(len_out)) {
     set_err(c, "edge_lengths: tetv must be 16-byte, skip / edge_out / len_out 8-byte aligned");
     return 0;
   }
@@ -707,7 +706,7 @@ int pmmg_hip_compute_wgt_mesh(pmmg_hip_ctx *c, int np, const double *xyz, int ne
     set_err(c, "compute_wgt_mesh: invalid arguments (np=%d ne=%d met_size=%d)", np, ne, met_size);
     return 0;
   }
-  if (ne > 0 && (!aligned16(tetv) || ((uintptr_t)ftag & 7))) {
+  if (ne > 0 && (!aligned<16>(tetv) || !aligned<8>(ftag))) {
     set_err(c, "compute_wgt_mesh: tetv must be 16-byte and ftag 8-byte aligned");
     return 0;
   }
@@ -726,7 +725,7 @@ int pmmg_hip_compute_wgt_faces(pmmg_hip_ctx *c, int np, const double *xyz, const
     set_err(c, "compute_wgt_faces: invalid arguments (np=%d nface=%d met_size=%d)", np, nface, met_size);
     return 0;
   }
-  if (nface > 0 && (!aligned16(tetv) || ((uintptr_t)face & 7))) {
+  if (nface > 0 && (!aligned<16>(tetv) || !aligned<8>(face))) {
     set_err(c, "compute_wgt_faces: tetv must be 16-byte and face 8-byte aligned");
     return 0;
   }
@@ -741,41 +740,41 @@ int pmmg_hip_metis_graph(pmmg_hip_ctx *c, int np, const double *xyz, int ne, con
                          const int *tet8, int met_size, const double *met, int cap, int64_t *nadjncy, int *xadj,
                          int *adjncy, int *adjwgt) {
   if (!enter(c)) return 0;
-  const bool packed = tet8 != nullptr, wgt = adjwgt != nullptr;
-  if (np < 0 || ne < 0 || !nadjncy || !xadj || cap < 0 || (cap > 0 && !adjncy) ||
-      (ne > 0 && !packed && !tetv && (!adja || wgt)) ||
+  const bool wgt = adjwgt != nullptr;
+  TetView m;
+  const TetArgs ta = tet_view(ne, tetv, adja, tet8, wgt ? TET_NEED_TETV : 0, &m);
+  if (np < 0 || ne < 0 || !nadjncy || !xadj || cap < 0 || (cap > 0 && !adjncy) || ta == TET_MISSING ||
       (wgt && ne > 0 && (np < 1 || !xyz || !valid_met_size(met_size) || (met_size && !met)))) {
     set_err(c, "metis_graph: invalid arguments (np=%d ne=%d met_size=%d cap=%d)", np, ne, met_size, cap);
     return 0;
   }
-  if (ne >= (1 << 29)) {
+  if (ta == TET_TOOMANY) {
     set_err(c, "metis_graph: %d tetra exceed the 4*k+i adjacency encoding (2^29)", ne);
     return 0;
   }
-  const int *t0 = packed ? tet8 : tetv, *a0 = packed ? tet8 + 4 : adja;
-  if (ne > 0 && (!aligned16(t0) || !aligned16(a0) || (wgt && (((uintptr_t)xyz & 7) || ((uintptr_t)met & 7))))) {
+  if (ta == TET_MISALIGNED || (ne > 0 && wgt && (!aligned<8>(xyz) || !aligned<8>(met)))) {
     set_err(c, "metis_graph: device tetra arrays must be 16-byte, xyz / met 8-byte aligned");
     return 0;
   }
-  if (((uintptr_t)xadj & 3) || ((uintptr_t)adjncy & 3) || ((uintptr_t)adjwgt & 3)) {
+  if (!aligned<4>(xadj) || !aligned<4>(adjncy) || !aligned<4>(adjwgt)) {
     set_err(c, "metis_graph: xadj / adjncy / adjwgt must be 4-byte aligned");
     return 0;
   }
-  if (ne > 0 && !a0 && np < 1) {
+  if (ne > 0 && !m.adja && np < 1) {
     set_err(c, "metis_graph: invalid arguments (np=%d: the adjacency is built from tetv)", np);
     return 0;
   }
-  return pmmg_graph_metis(c->stream, np, xyz, ne, t0, packed ? 2 : 1, a0, packed ? 2 : 1, wgt ? 1 : 0, met_size, met,
-                          cap, nadjncy, xadj, adjncy, adjwgt, &c->graph_cache, &c->snap_cache, c->err, sizeof(c->err));
+  return pmmg_graph_metis(c->stream, np, xyz, m, wgt ? 1 : 0, met_size, met, cap, nadjncy, xadj, adjncy, adjwgt,
+                          &c->graph_cache, &c->snap_cache, c->err, sizeof(c->err));
 }
 
 // ---- contiguity of a partition (pmmg_contig.hip)
 
 // the arguments the two contiguity calls share; fills *m
 static int contig_args(pmmg_hip_ctx *c, const char *who, int ne, const int *tetv, const int *adja, const int *tet8,
-                       const int *part, int ncolor, ContigMesh *m) {
-  const bool packed = tet8 != nullptr;
-  if (ne < 0 || ncolor < 1 || (ne > 0 && !packed && !tetv && !adja)) {
+                       const int *part, int ncolor, TetView *m) {
+  const TetArgs ta = tet_view(ne, tetv, adja, tet8, 0, m);
+  if (ne < 0 || ncolor < 1 || ta == TET_MISSING) {
     set_err(c, "%s: invalid arguments (ne=%d ncolor=%d)", who, ne, ncolor);
     return 0;
   }
@@ -783,16 +782,14 @@ static int contig_args(pmmg_hip_ctx *c, const char *who, int ne, const int *tetv
     set_err(c, "%s: part == NULL is one colour for the whole mesh: ncolor = %d must be 1", who, ncolor);
     return 0;
   }
-  if (ne >= (1 << 29)) {
+  if (ta == TET_TOOMANY) {
     set_err(c, "%s: %d tetra exceed the 4*k+i adjacency encoding (2^29)", who, ne);
     return 0;
   }
-  const int *t0 = packed ? tet8 : tetv, *a0 = packed ? tet8 + 4 : adja;
-  if (ne > 0 && (!aligned16(t0) || !aligned16(a0) || ((uintptr_t)part & 3))) {
+  if (ta == TET_MISALIGNED || (ne > 0 && !aligned<4>(part))) {
     set_err(c, "%s: device tetra arrays must be 16-byte, part 4-byte aligned", who);
     return 0;
   }
-  *m = ContigMesh{ne, t0, packed ? 2 : 1, a0, packed ? 2 : 1};
   return 1;
 }
 
@@ -800,9 +797,9 @@ int pmmg_hip_part_subgroups(pmmg_hip_ctx *c, int ne, const int *tetv, const int 
                             const int *part, int ncolor, int *head, int *flag, int *ncomp, int cap,
                             pmmg_hip_subgroup *sub, int64_t *nsub, int *rounds) {
   if (!enter(c)) return 0;
-  ContigMesh m;
+  TetView m;
   if (!contig_args(c, "part_subgroups", ne, tetv, adja, tet8, part, ncolor, &m)) return 0;
-  if (!ncomp || !nsub || cap < 0 || (cap > 0 && !sub) || ((uintptr_t)head & 3) || ((uintptr_t)flag & 3)) {
+  if (!ncomp || !nsub || cap < 0 || (cap > 0 && !sub) || !aligned<4>(head) || !aligned<4>(flag)) {
     set_err(c, "part_subgroups: invalid arguments (cap=%d; head / flag must be 4-byte aligned)", cap);
     return 0;
   }
@@ -813,7 +810,7 @@ int pmmg_hip_part_subgroups(pmmg_hip_ctx *c, int ne, const int *tetv, const int 
 int pmmg_hip_fix_contiguity(pmmg_hip_ctx *c, int ne, const int *tetv, const int *adja, const int *tet8, int *part,
                             int ncolor, int64_t *nmoved, int *nmerged, int *nstuck) {
   if (!enter(c)) return 0;
-  ContigMesh m;
+  TetView m;
   if (!contig_args(c, "fix_contiguity", ne, tetv, adja, tet8, part, ncolor, &m)) return 0;
   if (!nmoved || !nmerged || !nstuck) {
     set_err(c, "fix_contiguity: invalid arguments (a NULL counter)");
@@ -828,18 +825,17 @@ int64_t pmmg_hip_contig_passes(pmmg_hip_ctx *c) { return c ? c->contig_cache.pas
 int pmmg_hip_build_boundary(pmmg_hip_ctx *c, int np, int ne, const int *tet8, const int *tetv, const int *adja,
                             const int *tref, int cap, int *nt, int *triv, int *adjt) {
   if (!enter(c)) return 0;
-  const bool packed = tet8 != nullptr;
-  if (np <= 0 || ne <= 0 || !nt || (!packed && (!tetv || !adja)) || cap < 0 || (cap > 0 && !triv)) {
+  TetView m;
+  const TetArgs ta = tet_view(ne, tetv, adja, tet8, TET_NEED_TETV | TET_NEED_ADJA | TET_ANY_NE, &m);
+  if (np <= 0 || ne <= 0 || !nt || ta == TET_MISSING || cap < 0 || (cap > 0 && !triv)) {
     set_err(c, "build_boundary: invalid arguments (np=%d ne=%d cap=%d)", np, ne, cap);
     return 0;
   }
-  const int *t0 = packed ? tet8 : tetv, *a0 = packed ? tet8 + 4 : adja;
-  if (!aligned16(t0) || !aligned16(a0)) {
+  if (ta == TET_MISALIGNED) {
     set_err(c, "build_boundary: device tetra arrays must be 16-byte aligned");
     return 0;
   }
-  return pmmg_snap_boundary(c->stream, np, ne, t0, packed ? 2 : 1, a0, packed ? 2 : 1, tref, cap, nt, triv, adjt,
-                            &c->snap_cache, c->err, sizeof(c->err));
+  return pmmg_snap_boundary(c->stream, np, m, tref, cap, nt, triv, adjt, &c->snap_cache, c->err, sizeof(c->err));
 }
 
 void *pmmg_hip_malloc(pmmg_hip_ctx *c, int64_t bytes) {

@@ -382,15 +382,8 @@ __global__ __launch_bounds__(kSBlock) void k_edge_final(const Part *slab, int nb
 __global__ __launch_bounds__(kSBlock) void k_list_count(int ne, const unsigned char *mask, int *btot) {
   __shared__ int wt[kSWaves];
   const long long k = (long long)blockIdx.x * kSBlock + threadIdx.x;
-  int c = k < ne ? __popc((unsigned int)mask[k]) : 0;
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-  if ((threadIdx.x & 63) == 0) wt[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-    for (int w = 0; w < kSWaves; w++) s += wt[w];
-    btot[blockIdx.x] = s;
-  }
+  const int n = block_reduce<kSWaves>(k < ne ? __popc((unsigned int)mask[k]) : 0, wt, IntSum());
+  if (threadIdx.x == 0) btot[blockIdx.x] = n;
 }
 
 // boff[b]: analysed edges before block b.  Edge (k, ia) goes to row boff[b] + those before it in the
@@ -401,16 +394,8 @@ __global__ __launch_bounds__(kSBlock) void k_list_scatter(const double *xyz, int
   __shared__ int wt[kSWaves];
   const long long k = (long long)blockIdx.x * kSBlock + threadIdx.x;
   const unsigned int m = k < ne ? mask[k] : 0u;
-  const int c = __popc(m), lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = c; // inclusive prefix within the wave
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wt[w] = x;
-  __syncthreads();
-  int pos = boff[blockIdx.x] + x - c;
-  for (int i = 0; i < w; i++) pos += wt[i];
+  int n;
+  int pos = boff[blockIdx.x] + block_prefix<kSWaves>(__popc(m), wt, &n);
   if (!m) return;
   const int4 t = tetv[k];
   const int v[4] = {t.x, t.y, t.z, t.w};
@@ -439,7 +424,7 @@ constexpr int kSmallCnt = 32; // StatsCache::small: 32 counters, then the 2 flag
 int64_t pmmg_stats_cache_bytes(const StatsCache *c) {
   int64_t b = 0;
   if (c)
-    for (const DevBuf *d : {&c->keys, &c->own, &c->small, &c->slab, &c->mask, &c->res, &c->btot, &c->boff, &c->scan})
+    for (const DevBuf *d : {&c->keys, &c->own, &c->small, &c->slab, &c->mask, &c->res, &c->list.btot, &c->list.boff, &c->list.tmp})
       b += (int64_t)d->cap;
   return b;
 }
@@ -554,14 +539,11 @@ int pmmg_stats_edge_lengths(hipStream_t s, int np, const double *xyz, int ne, co
   }
   if (ne == 0) return 1;
   const int lblk = (ne + kSBlock - 1) / kSBlock;
-  int *btot = get<int>(cache->btot, (size_t)lblk), *boff = get<int>(cache->boff, (size_t)lblk);
-  if (!btot || !boff) {
-    snprintf(msg, msglen, "edge_lengths: out of device memory (list pass)");
-    return 0;
-  }
-  hipLaunchKernelGGL(k_list_count, dim3(lblk), dim3(kSBlock), 0, s, ne, mask, btot);
-  if (!exclusive_scan(cache->scan, btot, boff, lblk, s, msg, msglen)) return 0;
-  hipLaunchKernelGGL(k_list_scatter, dim3(lblk), dim3(kSBlock), 0, s, xyz, ne, tv, ani, met, mask, boff, cap,
+  if (!reserve(cache->list, lblk, s, "edge_lengths: out of device memory (list pass)", msg, msglen)) return 0;
+  hipLaunchKernelGGL(k_list_count, dim3(lblk), dim3(kSBlock), 0, s, ne, mask, cache->list.btot.as<int>());
+  if (!offsets(cache->list, s, lblk, nullptr, msg, msglen)) return 0; // (the total is out->nedge - out->nskipped)
+  hipLaunchKernelGGL(k_list_scatter, dim3(lblk), dim3(kSBlock), 0, s, xyz, ne, tv, ani, met, mask,
+                     cache->list.boff.as<int>(), cap,
                      reinterpret_cast<int2 *>(edge_out), len_out);
   DEVCK(hipGetLastError());
   DEVCK(hipStreamSynchronize(s));

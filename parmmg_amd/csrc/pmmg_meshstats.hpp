@@ -17,7 +17,7 @@ struct StatsCache {
   DevBuf small;      // 32 counters, then the 2 flags
   DevBuf slab, mask; // per-block partials; the tetra's owned-edge bits
   DevBuf res;        // the report on the device
-  DevBuf btot, boff, scan; // list pass: per-block counts, their offsets, the scan's temporary
+  BlockScan list;    // list pass: analysed edges per block, their offsets
   // the table size a call had to grow to, and the counts it was for: the next call on such a mesh starts there
   long long grown_nslot = 0;
   int grown_np = 0, grown_ne = 0, grown_nskip = 0, grown_mode = 0;

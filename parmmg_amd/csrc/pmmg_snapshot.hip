@@ -320,28 +320,6 @@ __device__ __forceinline__ int bdy_faces(const int4 &a, int k, const int *tref) 
   return bdy_face(a.x, k, tref) + bdy_face(a.y, k, tref) + bdy_face(a.z, k, tref) + bdy_face(a.w, k, tref);
 }
 
-// block-wide exclusive prefix of v (kB threads), and the block's total
-__device__ __forceinline__ int block_prefix(int v, int *wsum, int &total) {
-  const int lane = __lane_id(), w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(x, d);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) wsum[w] = x;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int j = 0; j < kB / 64; j++) {
-    before += j < w ? wsum[j] : 0;
-    total += wsum[j];
-  }
-  __syncthreads();
-  return before + x - v;
-}
-
 // Pass 1 over the tetra (r04): per block of kB tetra, its boundary faces'
 // count and its tetra with any, compacted in tetra order into the block's
 // own kB slots of cand (boundary tetra are few: pass 2 reads only those
@@ -354,7 +332,7 @@ __global__ __launch_bounds__(kB) void k_bdy_count(const int4 *adja, int astride,
   const int nb = k < ne ? bdy_faces(adja[(size_t)k * astride], k, tref) : 0;
   // one prefix over {candidate flag, face count} (<= 256 and <= 1024 per block)
   int tot = 0;
-  const int pos = block_prefix(((nb > 0) << 16) | nb, wsum, tot) >> 16;
+  const int pos = block_prefix<kB / 64>(((nb > 0) << 16) | nb, wsum, &tot) >> 16;
   if (nb > 0) cand[(size_t)blockIdx.x * kB + pos] = k;
   if (threadIdx.x == 0) {
     btot[blockIdx.x] = tot & 0xFFFF;
@@ -374,7 +352,7 @@ __global__ __launch_bounds__(kB) void k_bdy_write(const int4 *tetv, int tstride,
   const int4 a = in ? adja[(size_t)k * astride] : make_int4(1, 1, 1, 1);
   const int nb = in ? bdy_faces(a, k, tref) : 0;
   int tot = 0;
-  int pos = boff[blockIdx.x] + block_prefix(nb, wsum, tot);
+  int pos = boff[blockIdx.x] + block_prefix<kB / 64>(nb, wsum, &tot);
   if (!in) return;
   const int4 t = tetv[(size_t)k * tstride];
 #pragma unroll
@@ -461,7 +439,7 @@ int pmmg_snap_adjacency(hipStream_t s, int np, int ne, const int *tetv, int *adj
   const int4 *tv = reinterpret_cast<const int4 *>(tetv);
   hipLaunchKernelGGL(k_face_count, dim3(blocks(ne)), dim3(kB), 0, s, tv, ne, np, cnt, reinterpret_cast<int4 *>(tet8),
                      err);
-  if (!exclusive_scan(cache->scan, cnt, off, np, s, msg, msglen)) return 0;
+  if (!exclusive_scan(cache->blk.tmp, cnt, off, np, s, msg, msglen)) return 0;
   DEVCK(hipMemcpyAsync(cursor, off, sizeof(int) * (size_t)np, hipMemcpyDeviceToDevice, s));
   hipLaunchKernelGGL(k_face_scatter, dim3(blocks(ne)), dim3(kB), 0, s, tv, ne, np, cursor, bucket,
                      reinterpret_cast<int4 *>(adja), reinterpret_cast<int4 *>(tet8));
@@ -469,8 +447,7 @@ int pmmg_snap_adjacency(hipStream_t s, int np, int ne, const int *tetv, int *adj
                      adja, tet8, err);
   DEVCK(hipGetLastError());
   int h_err = 0;
-  DEVCK(hipMemcpyAsync(&h_err, err, sizeof(int), hipMemcpyDeviceToHost, s));
-  DEVCK(hipStreamSynchronize(s));
+  if (!read_word(s, err, &h_err, msg, msglen)) return 0;
   if (h_err & kErrIds) { snprintf(msg, msglen, "build_adjacency: vertex ids out of [1, np] or repeated in a tetra"); return 0; }
   if (h_err & kErrNonManifold) { snprintf(msg, msglen, "build_adjacency: a face is shared by more than two tetra"); return 0; }
   return 1;
@@ -491,13 +468,12 @@ int pmmg_snap_tria_adjacency(hipStream_t s, int np, int nt, const int *triv, int
   DEVCK(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)np, s));
   DEVCK(hipMemsetAsync(err, 0, sizeof(int), s));
   hipLaunchKernelGGL(k_edge_count, dim3(blocks(nedge)), dim3(kB), 0, s, triv, nt, np, cnt, rank, err);
-  if (!exclusive_scan(cache->scan, cnt, off, np, s, msg, msglen)) return 0;
+  if (!exclusive_scan(cache->blk.tmp, cnt, off, np, s, msg, msglen)) return 0;
   hipLaunchKernelGGL(k_edge_scatter, dim3(blocks(nedge)), dim3(kB), 0, s, triv, nt, off, rank, bucket);
   hipLaunchKernelGGL(k_edge_match, dim3(blocks(nedge)), dim3(kB), 0, s, triv, nt, off, cnt, bucket, adjt);
   DEVCK(hipGetLastError());
   int h_err = 0;
-  DEVCK(hipMemcpyAsync(&h_err, err, sizeof(int), hipMemcpyDeviceToHost, s));
-  DEVCK(hipStreamSynchronize(s));
+  if (!read_word(s, err, &h_err, msg, msglen)) return 0;
   if (h_err) {
     snprintf(msg, msglen, "tria adjacency: tria vertex ids out of [1, np]");
     return 0;
@@ -505,26 +481,24 @@ int pmmg_snap_tria_adjacency(hipStream_t s, int np, int nt, const int *triv, int
   return 1;
 }
 
-int pmmg_snap_boundary(hipStream_t s, int np, int ne, const int *tetv, int tstride, const int *adja, int astride,
-                       const int *tref, int cap, int *nt_out, int *triv, int *adjt, SnapCache *cache, char *msg,
-                       size_t msglen) {
-  const int nblk = blocks(ne);
-  int *cand = get<int>(cache->cand, (size_t)nblk * kB), *bs = get<int>(cache->blk, 3 * (size_t)nblk);
-  if (!cand || !bs) { snprintf(msg, msglen, "build_boundary: out of device memory"); return 0; }
-  int *btot = bs, *bcnt = bs + nblk, *boff = bs + 2 * (size_t)nblk;
-  const int4 *tv = reinterpret_cast<const int4 *>(tetv), *ad = reinterpret_cast<const int4 *>(adja);
-  hipLaunchKernelGGL(k_bdy_count, dim3(nblk), dim3(kB), 0, s, ad, astride, tref, ne, cand, btot, bcnt);
-  if (!exclusive_scan(cache->scan, btot, boff, nblk, s, msg, msglen)) return 0;
-  int last[2] = {0, 0};
-  DEVCK(hipMemcpyAsync(&last[0], boff + nblk - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-  DEVCK(hipMemcpyAsync(&last[1], btot + nblk - 1, sizeof(int), hipMemcpyDeviceToHost, s));
-  DEVCK(hipStreamSynchronize(s));
-  const int nt = last[0] + last[1];
+int pmmg_snap_boundary(hipStream_t s, int np, const TetView &m, const int *tref, int cap, int *nt_out, int *triv,
+                       int *adjt, SnapCache *cache, char *msg, size_t msglen) {
+  const int nblk = blocks(m.ne);
+  const char *oom = "build_boundary: out of device memory";
+  int *cand = get<int>(cache->cand, (size_t)nblk * kB), *bcnt = get<int>(cache->bcnt, (size_t)nblk);
+  if (!cand || !bcnt) return refuse(msg, msglen, oom);
+  if (!reserve(cache->blk, nblk, s, oom, msg, msglen)) return 0;
+  const int *boff = cache->blk.boff.as<int>();
+  const int4 *tv = reinterpret_cast<const int4 *>(m.tetv), *ad = reinterpret_cast<const int4 *>(m.adja);
+  hipLaunchKernelGGL(k_bdy_count, dim3(nblk), dim3(kB), 0, s, ad, m.astride, tref, m.ne, cand,
+                     cache->blk.btot.as<int>(), bcnt);
+  int nt = 0;
+  if (!offsets(cache->blk, s, nblk, &nt, msg, msglen)) return 0;
   *nt_out = nt;
   if (nt > cap) { snprintf(msg, msglen, "build_boundary: %d boundary trias exceed the capacity %d", nt, cap); return 0; }
   if (nt == 0) return 1;
-  hipLaunchKernelGGL(k_bdy_write, dim3(nblk), dim3(kB), 0, s, tv, tstride, ad, astride, tref, (const int *)cand,
-                     (const int *)bcnt, (const int *)boff, triv);
+  hipLaunchKernelGGL(k_bdy_write, dim3(nblk), dim3(kB), 0, s, tv, m.tstride, ad, m.astride, tref, (const int *)cand,
+                     (const int *)bcnt, boff, triv);
   DEVCK(hipGetLastError());
   if (adjt && !pmmg_snap_tria_adjacency(s, np, nt, triv, adjt, cache, msg, msglen)) return 0;
   DEVCK(hipStreamSynchronize(s));
