@@ -68,7 +68,7 @@ def build_hip(force: bool = False) -> str:
                                         "pmmg_meshstats.hpp", "pmmg_graph.hpp", "pmmg_sort.hpp", "pmmg_comm.hpp",
                                         "pmmg_devbuf.hpp", "pmmg_devutil.hpp", "pmmg_ctx.hpp", "pmmg_xfer.hpp",
                                         "pmmg_carry.hpp", "pmmg_call.hpp", "pmmg_groups.hpp", "pmmg_contig.hpp",
-                                        "pmmg_contig_decide.hpp", "pmmg_tetview.hpp")]
+                                        "pmmg_contig_decide.hpp", "pmmg_tetview.hpp", "pmmg_blockscan.hpp")]
     if force or _stale(out, deps):
         # max-memory-clause scheduling: the gathers of a step issued as clauses
         # (volume kernel -4.6 % at cfg4, same registers; profiles/r02e/sweep_sched_strategy.txt)

@@ -125,7 +125,7 @@ template <int MAP = 0>
 __global__ __launch_bounds__(kBlock) void k_bdy(Bg bg, const Frame *fr, const unsigned long long *sgrid, int gs,
                                                 const double *qxyz,
                                                 const int *order, Slots S, int *elem_out, int8_t *hit_out, int *fb,
-                                                DevStats *st, int maxstep, FbInit fi, FbGridBufs gb, MapArgs ma) {
+                                                DevStats *st, int maxstep, FbInit fi, MapArgs ma) {
   __shared__ BlockStats bs;
   bstats_init(&bs);
   __syncthreads();
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(kBlock) void k_bdy(Bg bg, const Frame *fr, const un
     }
     wave_count(&bs, kCntFanScan, active && scans > 0);
     if constexpr (MAP != 0) wave_count(&bs, kCntBdySrc, active && k0 != 0);
-    int slot = wave_append(&st->nfb_bdy, active && hit == 0);
+    int slot = wave_append(&st->fb[1].nfb, active && hit == 0);
     if (active && hit == 0) {
       fb[slot] = ip;
       fi.at(slot);

@@ -172,20 +172,24 @@ struct Call {
   }
 };
 
-// The exhaustive searches of one family (the volume queries' on the main stream after the exact continuation, the
-// surface queries' on the surface stream after k_bdy): the list's query grid, then the accepting and the closest
-// search, the last of which records `stop`.  The lists and their counts live on the device, every kernel reads its.
-template <class Accept, class Closest>
-static void launch_fallbacks(Call &k, const FbBufs &f, int cls, hipStream_t s, Accept accept, Closest closest,
-                             int blocks, hipEvent_t stop) {
+// The exhaustive searches of one class (NV = 4: the volume queries' on the main stream after the exact continuation,
+// 3: the surface queries' on the surface stream after k_bdy): the list's query grid, then the accepting and the
+// closest search, the last of which records `stop`.  The lists and their counts live on the device, every kernel
+// reads its; the grid is sized by the background (fb_blocks).
+template <int NV>
+static void launch_fallbacks(Call &k, hipStream_t s, hipEvent_t stop) {
+  using E = FbElem<NV>;
   const Bg &bg = k.c->bg;
+  const FbBufs &f = k.c->fb[E::cls];
   const int *fb = f.list.as<const int>();
-  hipLaunchKernelGGL(k_fb_grid, dim3(1), dim3(kBlock), 0, s, k.xyz_new, fb, k.st, cls, f.grid());
-  hipLaunchKernelGGL(accept, dim3(blocks), dim3(kBlock), 0, s, bg, k.xyz_new, fb, k.st, f.best.as<int>(),
-                     f.nac.as<int>(), f.g_cells.as<const int>(), f.g_items.as<const int>(), k.S, k.elem_out,
-                     k.hit_out);
-  hipExtLaunchKernelGGL(closest, dim3(blocks), dim3(kBlock), 0, s, nullptr, stop, 0, bg, k.xyz_new, fb, k.st,
-                        f.nac.as<const int>(), f.part.as<FbPart>(), f.cres.as<int>(), k.S, k.elem_out, k.hit_out);
+  const int blocks = fb_blocks<NV>(E::count(bg));
+  hipLaunchKernelGGL(k_fb_grid, dim3(1), dim3(kBlock), 0, s, k.xyz_new, fb, k.st, E::cls, f.grid());
+  hipLaunchKernelGGL(k_exhaust_accept<NV>, dim3(blocks), dim3(kBlock), 0, s, bg, k.xyz_new, fb, k.st,
+                     f.best.as<int>(), f.nac.as<int>(), f.g_cells.as<const int>(), f.g_items.as<const int>(), k.S,
+                     k.elem_out, k.hit_out);
+  hipExtLaunchKernelGGL(k_exhaust_closest<NV>, dim3(blocks), dim3(kBlock), 0, s, nullptr, stop, 0, bg, k.xyz_new, fb,
+                        k.st, f.nac.as<const int>(), f.part.as<FbPart>(), f.cres.as<int>(), k.S, k.elem_out,
+                        k.hit_out);
 }
 
 // ---- slots and layout: the arguments checked, the solutions' slots, the volume kernel for their layout, the
@@ -266,7 +270,7 @@ static int call_scratch(Call &k) {
       !ensure(c, c->grid, 8 * (size_t)k.ng) || !ensure(c, c->sgrid, 8 * (size_t)k.nsg) ||
       !ensure(c, c->order_v, 4 * nq) || !ensure(c, c->order_b, 4 * nq) || !ensure(c, c->bkeys, 4 * nq) ||
       !ensure(c, c->bkeys2, 4 * nq) || !ensure(c, c->bvals, 4 * nq) || !ensure(c, c->cls_cnt, 4 * (size_t)k.ncls) ||
-      !fb_scratch(c, c->fb_vol, nq, (size_t)kFbPartCap) || !fb_scratch(c, c->fb_bdy, nq, 256 * (size_t)kFbGridBdy))
+      !fb_scratch(c, c->fb[0], nq, kFbPartCap<4>) || !fb_scratch(c, c->fb[1], nq, kFbPartCap<3>))
     return 0;
   if (!ensure(c, c->xq, sizeof(int) * kXqStride * (size_t)bg.np) || !ensure(c, c->oflag, 2 * sizeof(int)) ||
       !ensure(c, c->cohd, sizeof(double) * kCohSamples) ||
@@ -447,8 +451,8 @@ static void launch_bdy(Call &k) {
   const auto bdy_fn = k.ma.src ? k_bdy<1> : k_bdy<0>;
   hipLaunchKernelGGL(bdy_fn, dim3(8 * blocks_for((k.np_new + 7) / 8, kBdyBpx)), dim3(kBlock), 0,
                      k.sb, k.bg, (const Frame *)k.fr, (const unsigned long long *)k.sgrid, k.gs, k.xyz_new,
-                     (const int *)k.order_b, k.S, k.elem_out, k.hit_out, c->fb_bdy.list.as<int>(), k.st, c->maxstep,
-                     c->fb_bdy.init(), c->fb_bdy.grid(), k.ma);
+                     (const int *)k.order_b, k.S, k.elem_out, k.hit_out, c->fb[1].list.as<int>(), k.st, c->maxstep,
+                     c->fb[1].init(), k.ma);
 }
 
 // (EV_BDY1 on the branch's last launch, when it has one)
@@ -456,11 +460,7 @@ static int srf_tail(Call &k) {
   pmmg_hip_ctx *c = k.c;
   const bool fill = k.nsg >= kRefillCells;
   if (k.bg.nt > 0) {
-    // grids sized by the background (a small group's empty fallback launches cost their dispatch: r04l, cfg2,
-    // ~4 us each at 1024 blocks)
-    const int gb = (int)std::min<long long>(kFbGridBdy, std::max<long long>(32, c->bg.nt / 4096)) & ~7;
-    launch_fallbacks(k, c->fb_bdy, 1, k.sb, k_bdy_exhaust_accept, k_bdy_exhaust_closest, gb,
-                     fill ? nullptr : k.mark(EV_BDY1));
+    launch_fallbacks<3>(k, k.sb, fill ? nullptr : k.mark(EV_BDY1));
     HIPCK(c, hipGetLastError());
     if (fill) { // the surface grid refilled for the next call (see k_reset)
       hipExtLaunchKernelGGL(k_fill64, dim3(blocks_for((k.nsg + 1) / 2, 2048)), dim3(kBlock), 0, k.sb, nullptr,
@@ -481,7 +481,7 @@ static int srf_tail(Call &k) {
 static int launch_vol(Call &k) {
   pmmg_hip_ctx *c = k.c;
   if (k.force != 0 && (!k.wait(k.s, EV_ORDER2) || !k.rec(EV_VOL0, k.s))) return 0;
-  const ContArgs ca{c->fb_vol.list.as<int>(), c->fb_vol.init(), c->maxstep};
+  const ContArgs ca{c->fb[0].list.as<int>(), c->fb[0].init(), c->maxstep};
   hipExtLaunchKernelGGL(k.vol_fn, dim3((k.np_new + 63) / 64), dim3(64), 0, k.s, nullptr, k.mark(EV_WALK), 0, k.bg,
                         (const Frame *)k.fr, (const unsigned long long *)k.grid, k.g, k.xyz_new, k.pclass,
                         (const int *)k.order_v, k.np_new, k.st, k.S, k.elem_out, k.hit_out, c->filter_steps, k.flag,
@@ -511,8 +511,7 @@ static int launch_tail(Call &k) {
   // exhaustive fallbacks of the volume queries (lists and counts on the
   // device; the surface ones ran on the surface stream after k_bdy): the
   // list's query grid, then the searches, the last of which records EV_JOIN
-  const int gv = (int)std::min<long long>(kFbGridVol, std::max<long long>(64, c->bg.ne / 16384)) & ~7;
-  launch_fallbacks(k, c->fb_vol, 0, s, k_vol_exhaust_accept, k_vol_exhaust_closest, gv, k.mark(EV_JOIN));
+  launch_fallbacks<4>(k, s, k.mark(EV_JOIN));
   HIPCK(c, hipGetLastError());
   if (!k.wait(s, EV_BDY1) || (refill && !k.wait(s, EV_FILL)) || !k.rec(EV_END, s)) return 0;
   c->pending = true;

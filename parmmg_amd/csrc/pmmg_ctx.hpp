@@ -54,7 +54,7 @@ struct CtxBufs {
   DevBuf cls_cnt;                         // per-block class counts (surface list compaction)
   DevBuf oflag;                           // the coherence test's {sorted, bin_bits} on the device
   DevBuf qmin;                               // tetra quality minimum (pmmg_hip_tetra_qual)
-  FbBufs fb_vol, fb_bdy; // the exhaustive searches of the volume and of the surface queries
+  FbBufs fb[2]; // the exhaustive searches of the volume (0) and of the surface (1) queries
   // host-mode staging
   DevBuf h_xyz, h_cls, h_met, h_elem, h_hit;
   std::vector<DevBuf> h_f;

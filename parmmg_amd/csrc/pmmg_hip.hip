@@ -7,7 +7,7 @@
 //                                                             acceptance and continuation + interpolation)
 //   PMMG_interp4bar_*        src/interpmesh_pmmg.c:206-270 -> vol_slot / vol_interp_packed in k_vol (pmmg_vol.hpp)
 //   PMMG_locatePointBdy      src/locate_pmmg.c:587-723     -> k_bdy (locate + interpolate)  (pmmg_bdy.hpp)
-//   exhaustive / closest     src/locate_pmmg.c:477-515, 737-770 -> k_*_exhaust_accept, k_*_exhaust_closest
+//   exhaustive / closest     src/locate_pmmg.c:477-515, 737-770 -> k_exhaust_accept<NV>, k_exhaust_closest<NV>
 //                                                             (pmmg_fallback.hpp)
 //   PMMG_locate_setStart     src/locate_pmmg.c:931-986     -> k_start_tet / k_start_tri and the MAP variants of
 //                                                             k_vol / k_bdy (USE_POINTMAP; pmmg_prep.hpp)

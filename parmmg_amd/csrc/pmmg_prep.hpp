@@ -1,6 +1,9 @@
 // pmmg_prep.hpp — per-call preparation kernels of the transfer step
-// (included by pmmg_hip.hip only): state reset, background frame, volume and
-// surface seed grids, and the query order.
+// (included by pmmg_hip.hip only): the call's counters and the state the walks
+// share with the exhaustive searches (DevStats), the state reset, the
+// background frame with the fixed-point copy and the seed grid's axis maps,
+// the volume and surface seed grids, the point map's start tables, and the
+// query order (coherence test, Morton keys, the surface list's compaction).
 //
 // The input-order coherence test runs on the device (in k_bbox: coherence_final's flag,
 // which a large auto-order call also reads back once, run_device); the Morton
@@ -8,6 +11,7 @@
 // gated on that flag, and the volume kernel reads it.
 #pragma once
 
+#include "pmmg_blockscan.hpp"
 #include "pmmg_device.hpp"
 
 namespace pmmg {
@@ -17,17 +21,19 @@ namespace pmmg {
 // summed on the host at pmmg_hip_sync): one counter address hit by every
 // workgroup serialises the atomics at one L2 channel (a returning per-wave
 // atomic on one address cost +4 ms on cfg4).
+// The exhaustive searches (pmmg_fallback.hpp) of one query class, 0: volume, 1: surface.
+struct FbState {
+  int nfb;          // the fallback list's length (the walks append: k_vol, k_bdy)
+  int nac;          // fallback queries no element accepted (the closest search's list)
+  unsigned done[2]; // blocks done with the accept / the closest kernel: the last one finishes
+  // the uniform grid over the list's queries (fb_grid_build): origin, inverse
+  // cell size, cells per axis (0: not built)
+  double lo[3], inv[3];
+  int n;
+};
 struct DevStats {
-  int nvol, nbdy;       // query counts (nvol: Morton path only; the input-order walk counts its own)
-  int nfb_vol, nfb_bdy; // fallback lists (exhaustive searches)
-  int nac_vol, nac_bdy; // fallback queries no element accepted (the closest searches' lists)
-  // uniform grids over each fallback list's queries (fb_grid_build): origin,
-  // inverse cell size, cells per axis (0: not built)
-  double fbg_lo[2][3], fbg_inv[2][3];
-  int fbg_n[2];
-  unsigned bdy_done;    // k_bdy blocks done (the surface list's grid)
-  unsigned fb_done[4];  // blocks done with an exhaustive kernel (volume accept / closest, surface accept /
-                        // closest): the last one finishes
+  int nvol, nbdy; // query counts (nvol: Morton path only; the input-order walk counts its own)
+  FbState fb[2];
 };
 
 // the exhaustive searches' per-query state, initialised where a query joins
@@ -35,6 +41,15 @@ struct DevStats {
 struct FbInit {
   int *best;
   __device__ __forceinline__ void at(int slot) const { best[slot] = INT_MAX; }
+};
+
+// a fallback list's query grid (pmmg_fallback.hpp): at most kFbGridMax cells per axis
+constexpr int kFbGridMax = 16;
+constexpr int kFbCells = kFbGridMax * kFbGridMax * kFbGridMax;
+struct FbGridBufs {
+  int *cells; // kFbCells + 1 starts
+  int *cur;   // kFbCells scratch
+  int *items; // one per list entry
 };
 
 constexpr int kStatParts = 256;
@@ -840,52 +855,28 @@ __global__ __launch_bounds__(kBlock) void k_map_count(const uint8_t *pclass, lon
 
 // ---------------------------------------------------------------- block scans
 //
-// block-level exclusive scans, and k_scan_top (one block: the exclusive scan
-// of a short array, e.g. per-block counts).  When `gate` is non-null the
-// kernel runs only if *gate == want.
+// k_scan_top (one block: the exclusive scan of a short array, e.g. per-block
+// counts) and the sizes of the chunked scans; the scan over a block is
+// block_prefix (pmmg_blockscan.hpp).  When `gate` is non-null a kernel runs
+// only if *gate == want.
 constexpr int kScanItems = 16, kScanChunk = kBlock * kScanItems;
-
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = __lane_id();
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-
-// exclusive scan of one int per thread over the block; the block total in *tot
-__device__ __forceinline__ int block_excl_scan(int v, int *tot) {
-  __shared__ int wsum[kBlock / 64];
-  const int inc = wave_incl_scan(v);
-  const int w = threadIdx.x >> 6;
-  if (__lane_id() == 63) wsum[w] = inc;
-  __syncthreads();
-  int pre = 0, all = 0;
-#pragma unroll
-  for (int j = 0; j < kBlock / 64; j++) {
-    pre += j < w ? wsum[j] : 0;
-    all += wsum[j];
-  }
-  __syncthreads();
-  *tot = all;
-  return pre + inc - v;
-}
+constexpr int kWaves = kBlock / 64;
 
 __device__ __forceinline__ bool gate_off(const int *gate, int want) { return gate && *gate != want; }
 
 // one block: bsum[0..nb) -> exclusive offsets in place; the total -> *total
 __global__ __launch_bounds__(kBlock) void k_scan_top(int *bsum, int nb, int *total, const int *gate, int want) {
   if (gate_off(gate, want)) return;
+  __shared__ int wt[kWaves];
   int carry = 0;
   for (int b0 = 0; b0 < nb; b0 += kBlock) {
     const int b = b0 + threadIdx.x;
     const int v = b < nb ? bsum[b] : 0;
     int tot;
-    const int pre = block_excl_scan(v, &tot);
+    const int pre = block_prefix<kWaves>(v, wt, &tot);
     if (b < nb) bsum[b] = carry + pre;
     carry += tot;
+    __syncthreads(); // wt is written again in the next round
   }
   if (threadIdx.x == 0 && total) *total = carry;
 }
@@ -914,8 +905,9 @@ __global__ __launch_bounds__(kBlock) void k_axis_map(const int *H, Frame *fr, in
     cnt[q] = v;
     s += v;
   }
+  __shared__ int wt[kWaves];
   int tot;
-  const int pre = block_excl_scan(s, &tot);
+  const int pre = block_prefix<kWaves>(s, wt, &tot);
   {
     int run = pre;
 #pragma unroll
@@ -1129,8 +1121,8 @@ __global__ __launch_bounds__(kBlock) void k_cls_count(const uint8_t *pclass, lon
                                                       const int *gate, int want) {
   if (gate_off(gate, want)) return;
   const long long i0 = (long long)blockIdx.x * kScanChunk + (long long)threadIdx.x * kScanItems;
-  int tot;
-  block_excl_scan(__popc(cls_bits(pclass, np, i0, cls)), &tot);
+  __shared__ int wt[kWaves];
+  const int tot = block_reduce<kWaves>(__popc(cls_bits(pclass, np, i0, cls)), wt, IntSum());
   if (threadIdx.x == 0) bcnt[blockIdx.x] = tot;
 }
 
@@ -1139,220 +1131,14 @@ __global__ __launch_bounds__(kBlock) void k_cls_scatter(const uint8_t *pclass, l
   if (gate_off(gate, want)) return;
   const long long i0 = (long long)blockIdx.x * kScanChunk + (long long)threadIdx.x * kScanItems;
   unsigned m = cls_bits(pclass, np, i0, cls);
+  __shared__ int wt[kWaves];
   int tot;
-  int pos = boff[blockIdx.x] + block_excl_scan(__popc(m), &tot);
+  int pos = boff[blockIdx.x] + block_prefix<kWaves>(__popc(m), wt, &tot);
   while (m) {
     const int j = __ffs(m) - 1;
     m &= m - 1;
     out[pos++] = (int)(i0 + j + 1);
   }
 }
-
-// ---------------------------------------------------------------- exhaustive-search helpers
-// (pmmg_fallback.hpp; the grids are built by k_fb_grid, after k_vol and k_bdy)
-
-// the last block of a grid to pass this point (after its device-scope
-// atomics) gets true: the other blocks' results are then visible to it.  The
-// barrier before the ticket: every wave of the block has issued its atomics
-// (r04l: without it a block's later waves could still be scanning when the
-// last block read the results — 4 surface points left unprocessed, once)
-// The last block of a grid to get here returns true.  wrote: this thread
-// stored data the last block reads; a block any of whose threads did
-// releases it first (__threadfence).  The release is an L2 write-back on
-// gfx950 (the XCDs' L2s are not coherent with each other): taken in every
-// block of k_bdy (808 blocks for a 205k-point group) it took the kernel 17 ->
-// 87 us and slowed the volume kernel beside it (r05h trace) — only the blocks
-// that appended to a fallback list pay it.
-__device__ __forceinline__ bool last_block(unsigned *done, bool wrote) {
-  if (__syncthreads_or(wrote)) __threadfence();
-  __shared__ bool last;
-  if (threadIdx.x == 0) last = atomicAdd(done, 1u) == gridDim.x - 1;
-  __syncthreads();
-  if (last) __threadfence();
-  return last;
-}
-
-__device__ __forceinline__ int load_agent(const int *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The bounding box of an element inflated so that every point its
-// acceptance test can pass lies inside.  Volume: every barycentric
-// coordinate > -EPS puts x within 3 EPS of the extent outside the vertices'
-// box (x_c = sum_i b_i p_ic, sum_i b_i = 1); the pad is 1e-4 of the extent
-// (33x that, room for the coordinates' rounding on any element with an
-// aspect ratio below ~1e10) plus 1e-12 of the coordinates' magnitude.
-// Surface: the projection is inside the tria within the same margin and
-// |dist| <= hausd along the unit normal.  A degenerate element (zero or
-// non-finite volume / area) gets an infinite box: every query takes the
-// reference's test there, as in the oracle.
-constexpr double kBoxRel = 1e-4, kBoxAbs = 1e-12;
-struct Box {
-  double lo[3], hi[3];
-};
-__device__ __forceinline__ bool in_box(const Box &b, const double *x) {
-  // NaN coordinates compare false everywhere and fall through to the test
-  return !(x[0] < b.lo[0] || x[0] > b.hi[0] || x[1] < b.lo[1] || x[1] > b.hi[1] || x[2] < b.lo[2] ||
-           x[2] > b.hi[2]);
-}
-template <int NV>
-__device__ __forceinline__ Box elem_box(const double (*p)[3], double extra, bool degenerate) {
-  Box b;
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    double lo = p[0][c], hi = p[0][c];
-#pragma unroll
-    for (int v = 1; v < NV; v++) {
-      lo = fmin(lo, p[v][c]);
-      hi = fmax(hi, p[v][c]);
-    }
-    const double pad = kBoxRel * (hi - lo) + kBoxAbs * fmax(fabs(lo), fabs(hi)) + extra + 1e-300;
-    b.lo[c] = degenerate ? -INFINITY : lo - pad;
-    b.hi[c] = degenerate ? INFINITY : hi + pad;
-  }
-  return b;
-}
-
-// ---------------------------------------------------------------- query grids
-//
-// The accept scans test an element only against the fallback queries in the
-// grid cells its inflated box covers (r05: against every query of the list,
-// the scan cost ne x nfb box tests — 92 ms for 2644 queries over 120M tetra
-// in a carried iteration).  The grid is built by the last block of the kernel
-// that finishes the list (k_vol, k_bdy): G^3 cells over the
-// queries' box, G = cbrt(nfb / 4) + 1 <= kFbGridMax; cells[c] .. cells[c + 1]
-// index items[], the list positions of cell c's queries.  A query inside an
-// element's box is in a cell of the box's (clamped) cell range, so the pairs
-// tested are a superset of the accepting pairs: the same results as the full
-// scan.
-constexpr int kFbGridMax = 16;
-constexpr int kFbCells = kFbGridMax * kFbGridMax * kFbGridMax;
-struct FbGridBufs {
-  int *cells; // kFbCells + 1 starts
-  int *cur;   // kFbCells scratch
-  int *items; // one per list entry
-};
-
-__device__ __forceinline__ int fb_cell1(double x, double lo, double inv, int G) {
-  const double t = (x - lo) * inv;
-  return t > 0.0 ? (t < (double)G ? (int)t : G - 1) : 0; // NaN -> 0, +inf -> G - 1
-}
-
-// one block: the grid of the list fb[0, nfb) (cls 0 volume, 1 surface);
-// cells[kFbCells + 1] starts, cur[kFbCells] scratch, items[nfb]
-__device__ __noinline__ void fb_grid_build(const double *qxyz, const int *fb, int nfb, DevStats *st, int cls,
-                                           int *cells, int *cur, int *items) {
-  __shared__ double rlo[3][kBlock / 64], rhi[3][kBlock / 64]; // per-wave partial boxes
-  __shared__ int sG;
-  const int t = threadIdx.x, nt = blockDim.x, w = t >> 6, nw = (nt + 63) >> 6;
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int j = t; j < nfb; j += nt) {
-    double x[3];
-    load_pt(qxyz, fb[j], x);
-    for (int d = 0; d < 3; d++) {
-      lo[d] = fmin(lo[d], x[d]);
-      hi[d] = fmax(hi[d], x[d]);
-    }
-  }
-  for (int d = 0; d < 3; d++)
-    for (int o = 32; o > 0; o >>= 1) {
-      lo[d] = fmin(lo[d], __shfl_xor(lo[d], o));
-      hi[d] = fmax(hi[d], __shfl_xor(hi[d], o));
-    }
-  if (__lane_id() == 0)
-    for (int d = 0; d < 3; d++) {
-      rlo[d][w] = lo[d];
-      rhi[d][w] = hi[d];
-    }
-  __syncthreads();
-  if (t == 0) {
-    for (int d = 0; d < 3; d++) {
-      double a = INFINITY, b = -INFINITY;
-      for (int i = 0; i < nw; i++) {
-        a = fmin(a, rlo[d][i]);
-        b = fmax(b, rhi[d][i]);
-      }
-      rlo[d][0] = a;
-      rhi[d][0] = b;
-    }
-    int G = (int)cbrt((double)nfb / 4.0) + 1;
-    G = G < 1 ? 1 : (G > kFbGridMax ? kFbGridMax : G);
-    for (int d = 0; d < 3; d++) {
-      const double e = rhi[d][0] - rlo[d][0];
-      st->fbg_lo[cls][d] = rlo[d][0];
-      st->fbg_inv[cls][d] = e > 0.0 ? (double)G / e : 0.0;
-    }
-    st->fbg_n[cls] = G;
-    sG = G;
-  }
-  __syncthreads();
-  const int G = sG, nc = G * G * G;
-  const double l0 = st->fbg_lo[cls][0], l1 = st->fbg_lo[cls][1], l2 = st->fbg_lo[cls][2];
-  const double i0 = st->fbg_inv[cls][0], i1 = st->fbg_inv[cls][1], i2 = st->fbg_inv[cls][2];
-  for (int c = t; c < nc; c += nt) cur[c] = 0;
-  __syncthreads();
-  for (int j = t; j < nfb; j += nt) {
-    double x[3];
-    load_pt(qxyz, fb[j], x);
-    const int c = fb_cell1(x[0], l0, i0, G) + G * (fb_cell1(x[1], l1, i1, G) + G * fb_cell1(x[2], l2, i2, G));
-    atomicAdd(&cur[c], 1);
-  }
-  __threadfence_block();
-  __syncthreads();
-  if (t == 0) { // exclusive scan (at most kFbCells entries, once per call with fallbacks)
-    int acc = 0;
-    for (int c = 0; c < nc; c++) {
-      const int v = cur[c];
-      cells[c] = acc;
-      cur[c] = acc;
-      acc += v;
-    }
-    cells[nc] = acc;
-  }
-  __threadfence_block();
-  __syncthreads();
-  for (int j = t; j < nfb; j += nt) {
-    double x[3];
-    load_pt(qxyz, fb[j], x);
-    const int c = fb_cell1(x[0], l0, i0, G) + G * (fb_cell1(x[1], l1, i1, G) + G * fb_cell1(x[2], l2, i2, G));
-    items[atomicAdd(&cur[c], 1)] = j;
-  }
-}
-
-// The query grid of a completed fallback list (cls 0: volume, 1: surface), one
-// block, launched after the kernel that completes the list (r06: before, the
-// last block of that kernel built it after a per-block ticket on one counter
-// — k_bdy's 4096 tickets alone serialised ~47 us of atomics at the end of
-// the surface branch, profiles/r06j); returns at once for an empty list
-__global__ __launch_bounds__(kBlock) void k_fb_grid(const double *qxyz, const int *fb, DevStats *st, int cls,
-                                                   FbGridBufs gb) {
-  const int nfb = cls == 0 ? st->nfb_vol : st->nfb_bdy;
-  if (nfb > 0) fb_grid_build(qxyz, fb, nfb, st, cls, gb.cells, gb.cur, gb.items);
-}
-
-// the queries of the cells an element's (inflated) box covers: visit(j) for
-// each list position j (the accept test itself); nothing when the box misses
-// the grid's box
-template <class F>
-__device__ __forceinline__ void fb_grid_visit(const DevStats *st, int cls, const int *cells, const int *items,
-                                              const Box &b, F &&visit) {
-  const int G = st->fbg_n[cls];
-  int a[3], e[3];
-  for (int d = 0; d < 3; d++) {
-    const double lo = st->fbg_lo[cls][d], inv = st->fbg_inv[cls][d];
-    const double hi = inv > 0.0 ? lo + (double)G / inv : lo;
-    if (b.hi[d] < lo || b.lo[d] > hi) return; // (NaN boxes: degenerate elements have infinite ones)
-    a[d] = fb_cell1(b.lo[d], lo, inv, G);
-    e[d] = fb_cell1(b.hi[d], lo, inv, G);
-  }
-  for (int z = a[2]; z <= e[2]; z++)
-    for (int y = a[1]; y <= e[1]; y++)
-      for (int x = a[0]; x <= e[0]; x++) {
-        const int c = x + G * (y + G * z);
-        for (int q = cells[c]; q < cells[c + 1]; q++) visit(items[q]);
-      }
-}
-
-// ---------------------------------------------------------------- accept scans
 
 } // namespace pmmg

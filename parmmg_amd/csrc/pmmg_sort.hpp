@@ -61,8 +61,9 @@ __global__ __launch_bounds__(kBlock) void k_rs_scan_local(int *a, int n, int *cs
     v[j] = i0 + j < n ? a[i0 + j] : 0;
     s += v[j];
   }
+  __shared__ int wt[kWaves];
   int tot;
-  int run = block_excl_scan(s, &tot);
+  int run = block_prefix<kWaves>(s, wt, &tot);
 #pragma unroll
   for (int j = 0; j < kScanItems; j++) {
     if (i0 + j < n) a[i0 + j] = run;
@@ -101,6 +102,7 @@ __global__ __launch_bounds__(kBlock) void k_rs_scatter(const unsigned *kin, cons
   __shared__ int lv[kRsTile];
   __shared__ int wdig[kBlock / 64][256]; // a wave's digit counts, then its keys' first local position per digit
   __shared__ int gdelta[256];            // global position - local position of each digit's keys
+  __shared__ int wt[kWaves];             // the block prefix's (barriers between its rounds: the tile loop's own)
   const int t = threadIdx.x, w = t >> 6, lane = __lane_id();
   const unsigned long long below = (1ULL << lane) - 1ULL;
   for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void k_rs_scatter(const unsigned *kin, cons
       tot_d += c[q];
     }
     int tot;
-    const int dstart = block_excl_scan(tot_d, &tot);
+    const int dstart = block_prefix<kWaves>(tot_d, wt, &tot);
     int acc = dstart;
 #pragma unroll
     for (int q = 0; q < kBlock / 64; q++) {

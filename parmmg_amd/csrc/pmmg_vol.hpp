@@ -1067,7 +1067,7 @@ __global__ __launch_bounds__(64) void k_vol(Bg bg, const Frame *fr, const unsign
       acc = st2 == 1;
     }
     const bool fail = more && !acc;
-    const int fslot = wave_append(&st->nfb_vol, fail);
+    const int fslot = wave_append(&st->fb[0].nfb, fail);
     if (fail) {
       ca.fb[fslot] = ip;
       ca.fi.at(fslot);

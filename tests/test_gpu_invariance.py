@@ -18,7 +18,7 @@ tests assert):
   * test_orientation: the vol < 0 branch of the fp32 filter (step_f32) and of
     exact_accept with the default walks (at least 20 % of the volume points end
     in an inverted tetra, accepted there by exact_accept), and the exhaustive
-    accept scan (k_vol_exhaust_accept: tet_bary and elem_box on inverted
+    accept scan (k_exhaust_accept<4>: tet_bary and elem_box on inverted
     tetra) under PMMG_HIP_MAXSTEP=1 (nvol_exhaust > 0, inverted tetra among
     its results);
   * test_device_offsets: the scalar side of k_quantize (xyz at +8), of
