@@ -115,7 +115,11 @@ typedef struct {
  *     pmmg_hip_stats_size()  == sizeof(pmmg_hip_stats)
  * and refuses a library that differs: the library writes a whole
  * pmmg_hip_stats into the caller's struct (round 5 appended nbdy_fanscan, so a
- * shim built against the round-4 header would have been overrun by 8 bytes). */
+ * shim built against the round-4 header would have been overrun by 8 bytes).
+ * Entry points added since (the group split) leave the version as it is: no
+ * existing signature or struct changed, so a shim built against the earlier
+ * header of version 6 runs unchanged against this library; a shim that needs a
+ * later entry point finds out from the symbol itself. */
 #define PMMG_HIP_ABI_VERSION 6
 int pmmg_hip_abi_version(void);
 int64_t pmmg_hip_stats_size(void);
@@ -634,6 +638,97 @@ int pmmg_hip_fix_contiguity(pmmg_hip_ctx *ctx, int ne, const int *tetv, const in
  * context's last contiguity call (reported by tools/contiguity_time.py); -1
  * without a context. */
 int64_t pmmg_hip_contig_passes(pmmg_hip_ctx *ctx);
+
+/* ---- Group split: the sub-meshes and interfaces of a partition -------------
+ * What the reference does with the repaired part: PMMG_split_grps
+ * (src/grpsplit_pmmg.c:1711) through PMMG_split_eachGrp (:1267-1445) and
+ * PMMG_splitGrps_fillGroup (:819-1094) cuts, for every colour, a mesh of its
+ * own out of the group.  The reference's loop is sequential; its result is a
+ * function of (tetv, adja, part), stated here and computed on the device.
+ * Device pointers unless marked host, synchronous, main stream only, 1-based
+ * ids; tetra from tet8 when non-NULL, else from tetv + adja (both needed).
+ *   Tetra.  The tetra of group g are the old tetra with part == g, in
+ *     ascending old id.  old_tet[ne] holds the old id of every new tetra, the
+ *     groups one after the other in colour order; new_tet[k] (may be NULL) is
+ *     the 1-based rank of old tetra k in its group (the reference's pt->flag).
+ *   Points.  Over the group's tetra in new order and the corners 0..3 of each,
+ *     a vertex gets the group's next id the first time it appears (:879-999).
+ *     A vertex used by several groups is a point of each.  tetv_out holds
+ *     these ids, old_pt the old id of every new point, groups concatenated.
+ *   Adjacency.  adja_out[new k][f] = 4*new_tet[j] + i where the old link 4j+i
+ *     stays inside the group; 0 where the neighbour has another colour or the
+ *     old entry was 0 (:1012-1076).  tet8_out packs {tetv_out, adja_out} rows.
+ *     Each of tetv_out, adja_out, tet8_out may be NULL.
+ *   Face list of group g (face2int_face_comm_index1 / _index2), in (new tetra
+ *     t, face f) order, t 1-based: an entry for (a) an old boundary face with
+ *     face_old >= 0: index1 = 12t + 3f + face_old % 3, index2 = face_old / 3;
+ *     (b) a face whose neighbour has another colour.  The side with the lower
+ *     colour owns the face; the owned faces are numbered nface0, nface0+1, ...
+ *     in (colour, new tetra, face) order over the whole call, and index2 is
+ *     that number on both sides.  On the owner's side iploc = 0; on the other
+ *     side iploc is the position, in MMG5_idir[f], of the owner's vertex
+ *     v[MMG5_idir[i][0]] (i the owner's face; :692-743).  index1 = 12t + 3f +
+ *     iploc.  *nface_end = nface0 + the number of owned faces.
+ *   Node list of group g (node2int_node_comm_index1 / _index2).  One counter
+ *     runs over the call: E, the entries appended so far, starting at nnode0.
+ *     The reference's int_node_comm->nitem counts appended entries, not
+ *     distinct nodes (:630 and :664 both increment it), so the positions have
+ *     gaps; this is reproduced.  A group appends two runs.  First, in
+ *     ascending new point id, every point of g that already has a position
+ *     (from node_pos, or given by a lower colour): index1 = the new id,
+ *     index2 = the position.  Then the group's new interface nodes: points
+ *     without a position on a face of g towards another colour, in order of
+ *     their first (new tetra, face, MMG5_idir[f][0..2]) occurrence (:606-637,
+ *     :1081-1091); the j-th (0-based) gets index2 = E' + j + 1, E' being E
+ *     after the first run.  *nnode_end is the final E.  A node's owner is the
+ *     lowest colour that has it on an interface face.
+ *   count[ngrp] (host) the tetra, points, face entries and node entries of
+ *     every group; group g's segments of the outputs start at the exclusive
+ *     prefix sums of count[].ne, .np, .nface, .nnode.
+ * Out of scope: xtetra / xpoint records; the MG_PARBDY / MG_PARBDYBDY tags
+ * (the two lists name exactly the faces and points that get them); ls / disp
+ * (gather them with pmmg_hip_gather_rows); reallocation and cleanMesh; the
+ * external (MPI) communicators.
+ * Returns 0 (message in pmmg_hip_last_error) with nothing written to any
+ * device output when a part value lies outside [0, ngrp), a tetra is unused
+ * (v[0] <= 0: the reference requires a packed mesh, :1461), a link lies
+ * outside [4, 4*ne+3], a vertex id lies outside [1, np], or ne >= 2^29.
+ * Returns 0 as well when a cap is smaller than its total: count, *nnode_end
+ * and *nface_end are still filled, old_tet / new_tet / tetv_out / adja_out /
+ * tet8_out may be written, and none of old_pt or the four lists is (call with
+ * caps of 0 to size: pmmg_hip_build_boundary's convention).  ne == 0 and empty
+ * colours are valid; their counts are 0.  tet8 / tetv / adja / tetv_out /
+ * adja_out / tet8_out 16-byte, every other array 4-byte aligned.  Scratch
+ * lives in the context (pmmg_hip_release_scratch).  Two calls on the same
+ * inputs give byte-identical outputs. */
+typedef struct { int ne, np, nface, nnode; } pmmg_hip_split_count;
+
+int pmmg_hip_split_groups(pmmg_hip_ctx *ctx, int np, int ne,
+        const int *tetv, const int *adja, const int *tet8,
+        const int *part, int ngrp,
+        const int *node_pos,   /* [np]   may be NULL: old node2int_node_comm_index2 of the point, -1 none   */
+        const int *face_old,   /* [4*ne] may be NULL: 3*pos + iploc of an old parallel face, -1 none        */
+        int nnode0, int nface0,/* int_node_comm->nitem / int_face_comm->nitem on entry                      */
+        pmmg_hip_split_count *count,            /* host [ngrp]: always filled on a valid input             */
+        int64_t pt_cap, int64_t face_cap, int64_t node_cap,
+        int *old_tet,          /* [ne]  old id of every new tetra, groups concatenated in colour order      */
+        int *new_tet,          /* [ne]  may be NULL: id of every old tetra inside its group (pt->flag)      */
+        int *tetv_out, int *adja_out, int *tet8_out,   /* [4ne],[4ne],[8ne]; each may be NULL               */
+        int *old_pt,           /* [pt_cap] old id of every new point, groups concatenated                   */
+        int *face_idx1, int *face_idx2,         /* [face_cap] face2int_face_comm_index1 / _index2           */
+        int *node_idx1, int *node_idx2,         /* [node_cap] node2int_node_comm_index1 / _index2           */
+        int *nnode_end, int *nface_end);        /* host: the two nitem on exit                              */
+
+/* out row r = in row src[r]-1, r < n, rows of `size` doubles: the point rows
+ * (xyz: 3), the metric and the fields of a group through its old_pt.  src
+ * 4-byte, in / out 8-byte aligned; every src[r] must name a row of `in` (not
+ * checked).  Synchronous. */
+int pmmg_hip_gather_rows(pmmg_hip_ctx *ctx, int64_t n, const int *src /*1-based*/, int size,
+                         const double *in, double *out);
+
+/* Diagnostic: first-use rounds of the context's last split (the most colours
+ * that met at one vertex; tools/split_groups_time.py); -1 without a context. */
+int pmmg_hip_split_rounds(pmmg_hip_ctx *ctx);
 
 /* ---- One group split over the GPUs of a node -------------
  * One process per GPU (ParMmg's MPI ranks; GPU = node-local rank,

@@ -73,6 +73,24 @@ class HipSubgroup(ctypes.Structure):
     _fields_ = [("color", c_int), ("head", c_int), ("size", c_int), ("exit", c_int)]
 
 
+class HipSplitCount(ctypes.Structure):
+    """``pmmg_hip_split_count`` of include/parmmg_hip.h."""
+
+    _fields_ = [("ne", c_int), ("np", c_int), ("nface", c_int), ("nnode", c_int)]
+
+
+class HostSplitResult(ctypes.Structure):
+    """``pmmg_split_result`` of csrc/pmmg_host.h."""
+
+    _fields_ = [
+        ("count", P(HipSplitCount)), ("npt", c_int64), ("nface", c_int64), ("nnode", c_int64),
+        ("old_tet", P(c_int)), ("new_tet", P(c_int)), ("tetv", P(c_int)), ("adja", P(c_int)), ("old_pt", P(c_int)),
+        ("xyz", P(c_double)), ("met", P(c_double)), ("met_size", c_int), ("nfield", c_int), ("fields", P(P(c_double))),
+        ("face_idx1", P(c_int)), ("face_idx2", P(c_int)), ("node_idx1", P(c_int)), ("node_idx2", P(c_int)),
+        ("nnode_end", c_int), ("nface_end", c_int),
+    ]
+
+
 class HipGroup(ctypes.Structure):
     """``pmmg_hip_group`` of include/parmmg_hip.h (device pointers)."""
 
@@ -131,6 +149,12 @@ HIP_API = {
     "pmmg_hip_fix_contiguity": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, P(c_int64),
                                         P(c_int), P(c_int)]),
     "pmmg_hip_contig_passes": (c_int64, [c_void_p]),
+    "pmmg_hip_split_groups": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                      c_void_p, c_int, c_int, P(HipSplitCount), c_int64, c_int64, c_int64, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, P(c_int), P(c_int)]),
+    "pmmg_hip_gather_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    "pmmg_hip_split_rounds": (c_int, [c_void_p]),
     "pmmg_hip_memcpy_h2d": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "pmmg_hip_memcpy_d2h": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "pmmg_hip_locate_interp_rec": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -207,6 +231,9 @@ HOST_API = {
     "pmmg_host_free": (None, [c_void_p]),
     "pmmg_check_part_contiguity": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "pmmg_fix_contiguity_split": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "pmmg_split_grps": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, P(HostSplitResult)]),
+    "pmmg_split_result_free": (None, [P(HostSplitResult)]),
     "pmmg_max_tet_extent": (c_double, [c_int, c_void_p, c_int, c_void_p]),
     "pmmg_shard_mark": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                                 c_void_p, P(c_int64)]),

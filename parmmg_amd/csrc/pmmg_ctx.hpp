@@ -24,6 +24,7 @@
 #include "pmmg_meshstats.hpp"
 #include "pmmg_graph.hpp"
 #include "pmmg_contig.hpp"
+#include "pmmg_split.hpp"
 
 using namespace pmmg;
 
@@ -62,6 +63,7 @@ struct CtxBufs {
   StatsCache stats_cache; // pmmg_hip_qual_histo / pmmg_hip_edge_lengths: edge table, slabs (pmmg_meshstats.hip)
   GraphCache graph_cache; // pmmg_hip_metis_graph: block counts, scan scratch, a built adjacency (pmmg_graph.hip)
   ContigCache contig_cache; // pmmg_hip_part_subgroups / pmmg_hip_fix_contiguity: labels, the table (pmmg_contig.hip)
+  SplitCache split_cache; // pmmg_hip_split_groups: the new order, first uses, masks and prefixes (pmmg_split.hip)
   struct Kept { // a carry-over slot (see pmmg_hip_ctx::carry_slot)
     DevBuf xyz, met;
     std::vector<DevBuf> f;

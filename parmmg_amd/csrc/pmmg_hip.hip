@@ -594,6 +594,7 @@ int pmmg_hip_release_scratch(pmmg_hip_ctx *c) {
   c->stats_cache = StatsCache{};
   c->graph_cache = GraphCache{};
   c->contig_cache = ContigCache{};
+  c->split_cache = SplitCache{};
   for (DevBuf *b : {&c->bvals2, &c->rs_hist, &c->rs_csum, &c->start_tab}) b->release();
   c->start_valid = false; // (the next call with a point map builds the start tables again)
   for (pmmg_hip_ctx *l : c->lanes) pmmg_hip_destroy(l);
@@ -821,6 +822,59 @@ int pmmg_hip_fix_contiguity(pmmg_hip_ctx *c, int ne, const int *tetv, const int 
 }
 
 int64_t pmmg_hip_contig_passes(pmmg_hip_ctx *c) { return c ? c->contig_cache.passes : -1; }
+
+// ---- group split (pmmg_split.hip)
+
+int pmmg_hip_split_groups(pmmg_hip_ctx *c, int np, int ne, const int *tetv, const int *adja, const int *tet8,
+                          const int *part, int ngrp, const int *node_pos, const int *face_old, int nnode0, int nface0,
+                          pmmg_hip_split_count *count, int64_t pt_cap, int64_t face_cap, int64_t node_cap, int *old_tet,
+                          int *new_tet, int *tetv_out, int *adja_out, int *tet8_out, int *old_pt, int *face_idx1,
+                          int *face_idx2, int *node_idx1, int *node_idx2, int *nnode_end, int *nface_end) {
+  if (!enter(c)) return 0;
+  SplitArgs a{np, TetView{}, part, ngrp, node_pos, face_old, nnode0, nface0, count, pt_cap, face_cap, node_cap,
+              old_tet, new_tet, tetv_out, adja_out, tet8_out, old_pt, face_idx1, face_idx2, node_idx1, node_idx2,
+              nnode_end, nface_end};
+  const TetArgs ta = tet_view(ne, tetv, adja, tet8, TET_NEED_TETV | TET_NEED_ADJA, &a.m);
+  if (np < 0 || ne < 0 || ngrp < 1 || nnode0 < 0 || nface0 < 0 || !count || !nnode_end || !nface_end || pt_cap < 0 ||
+      face_cap < 0 || node_cap < 0 || ta == TET_MISSING || (ne > 0 && (np < 1 || !part || !old_tet))) {
+    set_err(c, "split_groups: invalid arguments (np=%d ne=%d ngrp=%d nnode0=%d nface0=%d)", np, ne, ngrp, nnode0,
+            nface0);
+    return 0;
+  }
+  if (ta == TET_TOOMANY) {
+    set_err(c, "split_groups: %d tetra exceed the 4*k+i adjacency encoding (2^29)", ne);
+    return 0;
+  }
+  if (ta == TET_MISALIGNED || !aligned<16>(tetv_out) || !aligned<16>(adja_out) || !aligned<16>(tet8_out)) {
+    set_err(c, "split_groups: device tetra arrays (in and out) must be 16-byte aligned");
+    return 0;
+  }
+  for (const void *p : {(const void *)part, (const void *)node_pos, (const void *)face_old, (const void *)old_tet,
+                        (const void *)new_tet, (const void *)old_pt, (const void *)face_idx1, (const void *)face_idx2,
+                        (const void *)node_idx1, (const void *)node_idx2})
+    if (!aligned<4>(p)) {
+      set_err(c, "split_groups: part, the positions and the lists must be 4-byte aligned");
+      return 0;
+    }
+  return pmmg_split_groups(c->stream, a, &c->split_cache, c->err, sizeof(c->err));
+}
+
+int pmmg_hip_gather_rows(pmmg_hip_ctx *c, int64_t n, const int *src, int size, const double *in, double *out) {
+  if (!enter(c)) return 0;
+  if (n < 0 || size < 1 || (n > 0 && (!src || !in || !out))) {
+    set_err(c, "gather_rows: invalid arguments (n=%lld size=%d)", (long long)n, size);
+    return 0;
+  }
+  if (!aligned<4>(src) || !aligned<8>(in) || !aligned<8>(out)) {
+    set_err(c, "gather_rows: src must be 4-byte, in / out 8-byte aligned");
+    return 0;
+  }
+  if (!pmmg_split_gather(c->stream, n, src, size, in, out, c->err, sizeof(c->err))) return 0;
+  HIPCK(c, hipStreamSynchronize(c->stream));
+  return 1;
+}
+
+int pmmg_hip_split_rounds(pmmg_hip_ctx *c) { return c ? c->split_cache.rounds : -1; }
 
 int pmmg_hip_build_boundary(pmmg_hip_ctx *c, int np, int ne, const int *tet8, const int *tetv, const int *adja,
                             const int *tref, int cap, int *nt, int *triv, int *adjt) {

@@ -390,3 +390,154 @@ int pmmg_fix_contiguity_split(pmmg_hip_ctx *ctx, int ne, const int *tetv, const 
   return ok;
 }
 
+
+/* ---------------------------------------------------------------- group split */
+
+void pmmg_split_result_free(pmmg_split_result *r) {
+  if (!r) return;
+  void *p[] = {r->count, r->old_tet, r->new_tet, r->tetv, r->adja, r->old_pt, r->xyz, r->met,
+               r->face_idx1, r->face_idx2, r->node_idx1, r->node_idx2};
+  for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); i++) free(p[i]);
+  if (r->fields)
+    for (int i = 0; i < r->nfield; i++) free(r->fields[i]);
+  free(r->fields);
+  memset(r, 0, sizeof(*r));
+}
+
+/* n bytes of the device block d in a new host block (one byte when n == 0, so that NULL means failure) */
+static void *split_down(pmmg_hip_ctx *ctx, const void *d, int64_t n) {
+  void *h = malloc(n > 0 ? (size_t)n : 1);
+  if (h && n > 0 && !pmmg_hip_memcpy_d2h(ctx, h, d, n)) {
+    free(h);
+    h = NULL;
+  }
+  return h;
+}
+
+int pmmg_split_grps(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne, const int *tetv, const int *adja,
+                    const int *part, int ngrp, int met_size, const double *met, int nfield, const int *field_size,
+                    const double *const *fields, const int *node_pos, const int *face_old, int nnode0, int nface0,
+                    pmmg_split_result *out) {
+  if (!ctx) {
+    fprintf(stderr, "[parmmg_host] no HIP context: the group split has no CPU fallback\n");
+    return 0;
+  }
+  if (!out) return 0;
+  memset(out, 0, sizeof(*out));
+  if (np < 0 || ne < 0 || ngrp < 1 || nfield < 0 || (nfield > 0 && (!field_size || !fields)) ||
+      (ne > 0 && (!xyz || !tetv || !adja || !part)))
+    return 0;
+  if (!met) met_size = 0;
+  const int64_t nt = ne, i4 = (int64_t)sizeof(int), d8 = (int64_t)sizeof(double);
+  enum { D_TETV, D_ADJA, D_PART, D_NPOS, D_FOLD, D_XYZ, D_MET, D_OLDT, D_NEWT, D_TV, D_AD, D_OLDP, D_F1, D_F2, D_N1, D_N2,
+         D_ROWS, D_COUNT };
+  void *d[D_COUNT] = {NULL};
+  void **d_fields = NULL;
+  int ok = 1;
+#define UP(slot, src, bytes)                                                                   \
+  do {                                                                                         \
+    if (ok && (src) && (bytes) > 0) {                                                          \
+      d[slot] = pmmg_hip_malloc(ctx, (int64_t)(bytes));                                        \
+      ok = d[slot] != NULL && pmmg_hip_memcpy_h2d(ctx, d[slot], (src), (int64_t)(bytes));      \
+    }                                                                                          \
+  } while (0)
+#define ROOM(slot, bytes)                                                                      \
+  do {                                                                                         \
+    if (ok) ok = (d[slot] = pmmg_hip_malloc(ctx, (int64_t)(bytes) > 0 ? (int64_t)(bytes) : 16)) != NULL; \
+  } while (0)
+  UP(D_TETV, tetv, i4 * 4 * nt);
+  UP(D_ADJA, adja, i4 * 4 * nt);
+  UP(D_PART, part, i4 * nt);
+  UP(D_NPOS, node_pos, i4 * np);
+  UP(D_FOLD, face_old, i4 * 4 * nt);
+  ROOM(D_OLDT, i4 * nt);
+  ROOM(D_NEWT, i4 * nt);
+  ROOM(D_TV, i4 * 4 * nt);
+  ROOM(D_AD, i4 * 4 * nt);
+  out->count = (pmmg_hip_split_count *)calloc((size_t)ngrp, sizeof(pmmg_hip_split_count));
+  ok = ok && out->count;
+  /* caps of 0 size the lists: that call returns 0 with the counts filled unless every list is empty */
+  int sized = 0;
+  if (ok)
+    sized = pmmg_hip_split_groups(ctx, np, ne, (const int *)d[D_TETV], (const int *)d[D_ADJA], NULL,
+                                  (const int *)d[D_PART], ngrp, (const int *)d[D_NPOS], (const int *)d[D_FOLD], nnode0,
+                                  nface0, out->count, 0, 0, 0, (int *)d[D_OLDT], (int *)d[D_NEWT], (int *)d[D_TV],
+                                  (int *)d[D_AD], NULL, NULL, NULL, NULL, NULL, NULL, &out->nnode_end, &out->nface_end);
+  int64_t tot_ne = 0;
+  for (int g = 0; ok && g < ngrp; g++) {
+    tot_ne += out->count[g].ne;
+    out->npt += out->count[g].np;
+    out->nface += out->count[g].nface;
+    out->nnode += out->count[g].nnode;
+  }
+  if (ok && !sized && tot_ne != nt) ok = 0; /* a refusal: the counts were left at 0 */
+  ROOM(D_OLDP, i4 * out->npt);
+  ROOM(D_F1, i4 * out->nface);
+  ROOM(D_F2, i4 * out->nface);
+  ROOM(D_N1, i4 * out->nnode);
+  ROOM(D_N2, i4 * out->nnode);
+  if (ok && !sized)
+    ok = pmmg_hip_split_groups(ctx, np, ne, (const int *)d[D_TETV], (const int *)d[D_ADJA], NULL,
+                               (const int *)d[D_PART], ngrp, (const int *)d[D_NPOS], (const int *)d[D_FOLD], nnode0,
+                               nface0, out->count, out->npt, out->nface, out->nnode, (int *)d[D_OLDT],
+                               (int *)d[D_NEWT], (int *)d[D_TV], (int *)d[D_AD], NULL, (int *)d[D_OLDP], (int *)d[D_F1],
+                               (int *)d[D_F2], (int *)d[D_N1], (int *)d[D_N2], &out->nnode_end, &out->nface_end);
+  /* the point rows through old_pt: xyz, the metric, every field, one after the other through one device block */
+  int width = met_size > 3 ? met_size : 3;
+  for (int i = 0; i < nfield; i++)
+    if (field_size[i] > width) width = field_size[i];
+  UP(D_XYZ, xyz, d8 * 3 * np);
+  ROOM(D_ROWS, d8 * width * out->npt);
+  if (ok) ok = pmmg_hip_gather_rows(ctx, out->npt, (const int *)d[D_OLDP], 3, (const double *)d[D_XYZ], (double *)d[D_ROWS]);
+  if (ok) ok = (out->xyz = (double *)split_down(ctx, d[D_ROWS], d8 * 3 * out->npt)) != NULL;
+  if (met_size) {
+    UP(D_MET, met, d8 * met_size * np);
+    if (ok)
+      ok = pmmg_hip_gather_rows(ctx, out->npt, (const int *)d[D_OLDP], met_size, (const double *)d[D_MET],
+                                (double *)d[D_ROWS]);
+    if (ok) ok = (out->met = (double *)split_down(ctx, d[D_ROWS], d8 * met_size * out->npt)) != NULL;
+  }
+  out->met_size = met_size;
+  if (ok && nfield) {
+    out->fields = (double **)calloc((size_t)nfield, sizeof(double *));
+    d_fields = (void **)calloc((size_t)nfield, sizeof(void *));
+    ok = out->fields && d_fields;
+    out->nfield = ok ? nfield : 0;
+  }
+  for (int i = 0; ok && i < nfield; i++) {
+    const int64_t bytes = d8 * field_size[i] * np;
+    if (field_size[i] < 1 || !fields[i]) {
+      ok = 0;
+      break;
+    }
+    if (bytes > 0) {
+      d_fields[i] = pmmg_hip_malloc(ctx, bytes);
+      ok = d_fields[i] != NULL && pmmg_hip_memcpy_h2d(ctx, d_fields[i], fields[i], bytes);
+    }
+    if (ok)
+      ok = pmmg_hip_gather_rows(ctx, out->npt, (const int *)d[D_OLDP], field_size[i], (const double *)d_fields[i],
+                                (double *)d[D_ROWS]);
+    if (ok) ok = (out->fields[i] = (double *)split_down(ctx, d[D_ROWS], d8 * field_size[i] * out->npt)) != NULL;
+  }
+#undef UP
+#undef ROOM
+  if (ok) {
+    ok = (out->old_tet = (int *)split_down(ctx, d[D_OLDT], i4 * nt)) != NULL &&
+         (out->new_tet = (int *)split_down(ctx, d[D_NEWT], i4 * nt)) != NULL &&
+         (out->tetv = (int *)split_down(ctx, d[D_TV], i4 * 4 * nt)) != NULL &&
+         (out->adja = (int *)split_down(ctx, d[D_AD], i4 * 4 * nt)) != NULL &&
+         (out->old_pt = (int *)split_down(ctx, d[D_OLDP], i4 * out->npt)) != NULL &&
+         (out->face_idx1 = (int *)split_down(ctx, d[D_F1], i4 * out->nface)) != NULL &&
+         (out->face_idx2 = (int *)split_down(ctx, d[D_F2], i4 * out->nface)) != NULL &&
+         (out->node_idx1 = (int *)split_down(ctx, d[D_N1], i4 * out->nnode)) != NULL &&
+         (out->node_idx2 = (int *)split_down(ctx, d[D_N2], i4 * out->nnode)) != NULL;
+  }
+  for (int i = 0; i < D_COUNT; i++)
+    if (d[i]) pmmg_hip_free(ctx, d[i]);
+  if (d_fields)
+    for (int i = 0; i < nfield; i++)
+      if (d_fields[i]) pmmg_hip_free(ctx, d_fields[i]);
+  free(d_fields);
+  if (!ok) pmmg_split_result_free(out);
+  return ok;
+}

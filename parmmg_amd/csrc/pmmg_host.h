@@ -157,6 +157,39 @@ int pmmg_check_part_contiguity(pmmg_hip_ctx *ctx, int ne, const int *tetv, const
  * include/parmmg_hip.h describes.  Returns 1, or 0 with part unchanged. */
 int pmmg_fix_contiguity_split(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *adja, int ngrp, int *part);
 
+/* ---- Group split ------------------------------------------------------------
+ * PMMG_split_grps (src/grpsplit_pmmg.c:1464) on host arrays in the "row r =
+ * entity r+1" layout, through pmmg_hip_split_groups and pmmg_hip_gather_rows:
+ * the mesh, part[ne] in [0, ngrp), the old communicator positions (node_pos
+ * [np] and face_old [4*ne], each may be NULL) go up; the groups are cut on
+ * the device; xyz, the metric (met NULL: none) and every field are gathered
+ * there through old_pt; everything comes back in arrays this call allocates,
+ * the groups one after the other (group g's segments start at the exclusive
+ * prefix sums of count[].ne, .np, .nface, .nnode).  Release them with
+ * pmmg_split_result_free, or one by one with pmmg_host_free.  What the arrays
+ * hold, and what of the reference's split is out of scope, is stated in
+ * include/parmmg_hip.h.  Returns 1, or 0 as the reference does, with *out
+ * zeroed (the reason in pmmg_hip_last_error). */
+typedef struct {
+  pmmg_hip_split_count *count;        /* [ngrp] */
+  int64_t npt, nface, nnode;          /* the sums of count[].np, .nface, .nnode */
+  int *old_tet, *new_tet;             /* [ne] */
+  int *tetv, *adja;                   /* [4*ne] new ids */
+  int *old_pt;                        /* [npt] */
+  double *xyz, *met;                  /* [3*npt], [met_size*npt] (NULL without a metric) */
+  int met_size, nfield;
+  double **fields;                    /* nfield arrays [field_size[i]*npt] */
+  int *face_idx1, *face_idx2;         /* [nface] */
+  int *node_idx1, *node_idx2;         /* [nnode] */
+  int nnode_end, nface_end;           /* the two nitem on exit */
+} pmmg_split_result;
+
+int pmmg_split_grps(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne, const int *tetv, const int *adja,
+                    const int *part, int ngrp, int met_size, const double *met, int nfield, const int *field_size,
+                    const double *const *fields, const int *node_pos, const int *face_old, int nnode0, int nface0,
+                    pmmg_split_result *out);
+void pmmg_split_result_free(pmmg_split_result *r);
+
 /* ---- halo shards of a background group (pmmg_shard.c) ----
  * All arrays in the "row r = entity r+1" layout of parmmg_hip.h. */
 

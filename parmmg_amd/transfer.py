@@ -17,7 +17,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._native import HipGroup, HipLenHisto, HipQualHisto, HipStats, HipSubgroup, hip_lib, host_lib
+from ._native import HipGroup, HipLenHisto, HipQualHisto, HipSplitCount, HipStats, HipSubgroup, hip_lib, host_lib
 
 HOST, DEVICE = 0, 1
 PT_SKIP, PT_VOL, PT_BDY = 0, 1, 2
@@ -313,8 +313,8 @@ class TransferContext:
 
     def release_scratch(self) -> None:
         """pmmg_hip_release_scratch: free the snapshot buckets, the binning's
-        scratch, the reports' edge table, the element graph's and the contiguity calls' scratch and the group
-        lanes (re-allocated on demand)."""
+        scratch, the reports' edge table, the element graph's, the contiguity calls' and the group split's
+        scratch and the group lanes (re-allocated on demand)."""
         self._ck(self.lib.pmmg_hip_release_scratch(self.h), "release_scratch")
 
     def bytes_up(self, reset: bool = False) -> int:
@@ -481,6 +481,118 @@ class TransferContext:
                  "fix_contiguity")
         return dict(nmoved=nmoved.value, nmerged=nmerged.value, nstuck=nstuck.value,
                     passes=int(self.lib.pmmg_hip_contig_passes(self.h)))
+
+    # ------------------------------------------------------------------ group split
+    def split_groups(self, npt, part, ngrp, tetv=None, adja=None, tet8=None, node_pos=None, face_old=None, nnode0=0,
+                     nface0=0, caps=None, want=("new_tet", "tet8_out")):
+        """PMMG_split_grps on the device (pmmg_hip_split_groups): device
+        arrays in, device arrays out.  Tetra from tet8 when given, else from
+        tetv + adja; part [ne] in [0, ngrp).  want: which of new_tet, tetv_out,
+        adja_out, tet8_out to write.  caps = (pt_cap, face_cap, node_cap), or
+        None: a first call with caps of 0 sizes the lists.  Returns a dict:
+        count [ngrp, 4] = ne, np, nface, nnode per group (host), the offset
+        tables te_off, pt_off, face_off, node_off [ngrp + 1] (host, exclusive
+        prefix sums of the counts), old_tet and the arrays of `want` [ne], old_pt,
+        face_idx1, face_idx2, node_idx1, node_idx2 (DeviceArrays of exactly
+        the lists' lengths, groups concatenated), nnode_end, nface_end,
+        rounds."""
+        given = [a for a in (tetv, adja, tet8, part, node_pos, face_old) if a is not None]
+        if not all(_is_dev(a) for a in given):
+            raise ValueError("split_groups takes device arrays")
+        unknown = set(want) - {"new_tet", "tetv_out", "adja_out", "tet8_out"}
+        if unknown:
+            raise ValueError(f"split_groups: unknown outputs {sorted(unknown)}")
+        ne, ngrp = int((tet8 if tet8 is not None else tetv).shape[0]), int(ngrp)
+        count = (HipSplitCount * max(1, ngrp))()
+        nn, nf = ctypes.c_int(0), ctypes.c_int(0)
+        out = dict(old_tet=self.empty((ne,), np.int32))
+        for k, cols in (("new_tet", None), ("tetv_out", 4), ("adja_out", 4), ("tet8_out", 8)):
+            out[k] = self.empty((ne,) if cols is None else (ne, cols), np.int32) if k in want else None
+
+        def call(caps_, lists):
+            return self.lib.pmmg_hip_split_groups(
+                self.h, int(npt), ne, _p(tetv), _p(adja), _p(tet8), _p(part), ngrp, _p(node_pos), _p(face_old),
+                int(nnode0), int(nface0), count, int(caps_[0]), int(caps_[1]), int(caps_[2]), _p(out["old_tet"]),
+                _p(out["new_tet"]), _p(out["tetv_out"]), _p(out["adja_out"]), _p(out["tet8_out"]), *[_p(a) for a in lists],
+                ctypes.byref(nn), ctypes.byref(nf))
+
+        def totals():
+            c = np.array([(r.ne, r.np, r.nface, r.nnode) for r in count[:ngrp]], np.int64).reshape(-1, 4)
+            return c, [int(x) for x in c.sum(axis=0)]
+
+        try:
+            if caps is None:
+                if not call((0, 0, 0), [None] * 5):
+                    c, tot = totals()
+                    if tot[0] != ne:  # (a refusal, not a cap: the counts were not filled)
+                        self._ck(0, "split_groups")
+                    caps = tot[1:]
+                else:
+                    caps = (0, 0, 0)
+            lists = [self.empty((int(caps[0]),), np.int32)] + [self.empty((int(caps[1]),), np.int32) for _ in range(2)]
+            lists += [self.empty((int(caps[2]),), np.int32) for _ in range(2)]
+            try:
+                self._ck(call(caps, lists), "split_groups")
+            except Exception:
+                for a in lists:
+                    a.free()
+                raise
+        except Exception:
+            for a in out.values():
+                if a is not None:
+                    a.free()
+            raise
+        c, tot = totals()
+        for a, n in zip(lists, (tot[1], tot[2], tot[2], tot[3], tot[3])):  # (a cap may exceed its list)
+            a.shape, a.nbytes = (n,), 4 * n
+        off = np.concatenate([np.zeros((1, 4), np.int64), np.cumsum(c, axis=0)])
+        out.update(count=c.astype(np.int32), te_off=off[:, 0], pt_off=off[:, 1], face_off=off[:, 2], node_off=off[:, 3],
+                   old_pt=lists[0], face_idx1=lists[1], face_idx2=lists[2], node_idx1=lists[3], node_idx2=lists[4],
+                   nnode_end=nn.value, nface_end=nf.value, rounds=int(self.lib.pmmg_hip_split_rounds(self.h)))
+        return out
+
+    def gather_rows(self, src, rows, out=None):
+        """out row r = rows row src[r] - 1 on the device (pmmg_hip_gather_rows):
+        src int32 [n] 1-based, rows float64 [m, size].  Returns the DeviceArray
+        [n, size] (out, when given)."""
+        if not (_is_dev(src) and _is_dev(rows) and (out is None or _is_dev(out))):
+            raise ValueError("gather_rows takes device arrays")
+        n, size = int(src.shape[0]), int(rows.shape[1])
+        if out is None:
+            out = self.empty((n, size), np.float64)
+        self._ck(self.lib.pmmg_hip_gather_rows(self.h, n, _p(src), size, _p(rows), _p(out)), "gather_rows")
+        return out
+
+    def groups_from_split(self, split, xyz, met=None, fields=()):
+        """The background part of every group's pmmg_hip_group record from a
+        split: a list of dicts {np, ne, xyz, tet8 | (tetv, adja), met, fields},
+        whose arrays are views into `split`'s arrays and into the rows
+        gathered here through old_pt (xyz, the metric, every field; device
+        arrays [np_old, size]).  Complete each dict with triv / adjt / hausd
+        and the new points, then pass the list to locate_interp_groups: nothing
+        goes through the host.  The views own no memory: free the returned
+        "owned" arrays and the split's, not the groups'."""
+        old_pt = split["old_pt"]
+        g_xyz = self.gather_rows(old_pt, xyz)
+        g_met = None if met is None else self.gather_rows(old_pt, met)
+        g_f = [self.gather_rows(old_pt, f) for f in fields]
+
+        def view(a, lo, hi):
+            row = a.nbytes // max(1, a.shape[0])
+            return DeviceArray(a.ptr + int(lo) * row, int(hi - lo) * row, (int(hi - lo),) + tuple(a.shape[1:]), a.dtype,
+                               self)
+
+        groups = []
+        for g in range(split["count"].shape[0]):
+            t0, t1, p0, p1 = split["te_off"][g], split["te_off"][g + 1], split["pt_off"][g], split["pt_off"][g + 1]
+            d = dict(np=int(p1 - p0), ne=int(t1 - t0), xyz=view(g_xyz, p0, p1), met=None if g_met is None else view(g_met, p0, p1),
+                     fields=[view(f, p0, p1) for f in g_f])
+            if split.get("tet8_out") is not None:
+                d["tet8"] = view(split["tet8_out"], t0, t1)
+            else:
+                d["tetv"], d["adja"] = view(split["tetv_out"], t0, t1), view(split["adja_out"], t0, t1)
+            groups.append(d)
+        return groups, [g_xyz] + ([] if g_met is None else [g_met]) + g_f
 
     # ------------------------------------------------------------------ split over GPUs (RCCL)
     @staticmethod
