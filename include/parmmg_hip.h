@@ -116,7 +116,7 @@ typedef struct {
  * and refuses a library that differs: the library writes a whole
  * pmmg_hip_stats into the caller's struct (round 5 appended nbdy_fanscan, so a
  * shim built against the round-4 header would have been overrun by 8 bytes).
- * Entry points added since (the group split) leave the version as it is: no
+ * Entry points added since (the group split, the interface displacement) leave the version as it is: no
  * existing signature or struct changed, so a shim built against the earlier
  * header of version 6 runs unchanged against this library; a shim that needs a
  * later entry point finds out from the symbol itself. */
@@ -729,6 +729,104 @@ int pmmg_hip_gather_rows(pmmg_hip_ctx *ctx, int64_t n, const int *src /*1-based*
 /* Diagnostic: first-use rounds of the context's last split (the most colours
  * that met at one vertex; tools/split_groups_time.py); -1 without a context. */
 int pmmg_hip_split_rounds(pmmg_hip_ctx *ctx);
+
+/* ---- Interface displacement: move the group fronts by layers ----------------
+ * PMMG_mark_interfacePoints and the layer loop of PMMG_part_moveInterfaces
+ * (src/moveinterfaces_pmmg.c:1052-1090, :1366-1439; PMMG_REDISTRIBUTION_
+ * ifc_displacement, called from PMMG_split_n2mGrps before every group
+ * redistribution), as a function of their inputs: the old groups' interfaces
+ * advance by layers of vertex stars into the group of larger weight.  Followed
+ * by pmmg_hip_fix_contiguity (:1446) the marks are the `part` that
+ * pmmg_hip_split_groups consumes.  PMMG_check_reachability and the MPI
+ * exchange between two layers stay with the shim.
+ *
+ * Colours are indices in [0, ncolor) (the shim maps its nprocs*igrp+rank ids);
+ * weight[c] > 0 is the priority map's entry (mapgrp: the group's tetra
+ * count); "c beats d" means weight[c] < weight[d], strictly
+ * (PMMG_get_ifcDirection(d, c) == 1).  A used tetra has v[0] > 0; an unused
+ * one never changes and never influences anything.  Ids are 1-based; point p
+ * is entry p-1 of ptcolor / ptfront.
+ *
+ * Seed.  ptcolor[p] is the mark at the lowest corner 4*ie+iloc of p whose
+ * weight is the minimum over p's corners; p is front iff the mark at p's
+ * lowest corner does not have that minimum weight (the reference flags a
+ * point only when its colour changes after its first corner: an interface
+ * point whose first tetra already holds the winning colour is not front).  A
+ * point of no used tetra gets colour -1 and is not front.
+ *
+ * One layer.  The front points' colours do not change during a layer.
+ *  1. Each used tetra T takes its front points in ascending id and keeps a
+ *     running strict minimum of weight that starts at its own mark.  Every
+ *     point whose colour beats the running colour is an event (T, ip, C =
+ *     ptcolor[ip], previous colour).  T's new mark is the last event's colour;
+ *     between equal weights the lower ip wins.
+ *  2. A point q off the front in a tetra with an event is front for the next
+ *     layer.  It takes the colour of the event of least (weight[C], ip) over
+ *     all events of the tetra that contain q, if that colour beats ptcolor[q].
+ *  3. A front point other than ip in a tetra with an event is a side point: it
+ *     takes the new mark of the tetra of least (weight, tetra id) among all
+ *     tetra that contain it, if that beats its own colour, and is front for
+ *     the next layer.
+ *  4. Every other front point leaves the front.
+ *  5. Before every layer the points of set_pt (a shim's communicator points)
+ *     become front; before the first layer of a call they take set_color[i]
+ *     when it is given.  The entries of set_pt are distinct.
+ *
+ * The brake.  Every event whose previous colour g is local (nelem[g] >= 0;
+ * -1: not local) takes one off nelem[g], the events between the first and the
+ * last of a tetra included, whose colour never gained the tetra.  The
+ * reference stops in the middle of a ball when a count reaches nemin[g] =
+ * MG_MIN(PMMG_REDISTR_NELEM_MIN = 6, negrp0/2 + 1); what it leaves then
+ * depends on its traversal order and is not computed here.  With D[g] the
+ * layer's events by previous colour, no brake fires in the layer iff D[g] <=
+ * nelem[g] - nemin[g] for every local g with D[g] > 0.  A layer is computed
+ * into scratch and committed only if that holds; otherwise nothing of that
+ * layer is committed, *blocked = 1, *layers_done counts the layers before it
+ * and every output holds their result, without the set points of the layer
+ * that was dropped: the state the reference is in before that layer, from
+ * which a shim finishes with the reference's own loop.
+ *
+ * Two deliberate deviations (pinned by tests/
+ * test_moveifc_ref_host.py).  Side points: between two different colours of
+ * equal least weight the reference takes the first tetra in its BFS order, the
+ * module the lowest tetra id.  Ball and star: the reference's ball is the
+ * face-connected part of the vertex star around the point's handle s, the
+ * module's is the whole star; s is not an output, and the MMG3D_LMAX overflow
+ * failure has no counterpart.
+ *
+ * Pointers are device pointers unless marked host.  Synchronous, main stream
+ * only.  tet8 wins over tetv; either gives the vertices (the links are not
+ * read).  Returns 0 with a message and nothing written: a mark of a used tetra
+ * or a colour outside [0, ncolor), weight[c] <= 0, a vertex id outside [1, np],
+ * a set_pt entry outside [1, np], ne >= 2^29, tet8 / tetv not 16-byte or
+ * another device array not 4-byte aligned (ptfront: any).  Scratch lives in a
+ * cache of its own in the context (pmmg_hip_release_scratch).  Two calls on
+ * the same inputs give byte-identical outputs. */
+int pmmg_hip_ifc_seed(pmmg_hip_ctx *ctx, int np, int ne, const int *tetv, const int *tet8,
+        const int *mark,              /* [ne]                                                  */
+        int ncolor, const int *weight,/* host [ncolor]                                         */
+        int *ptcolor,                 /* [np] out                                              */
+        unsigned char *ptfront);      /* [np] out: 1 front, 0 not                              */
+
+int pmmg_hip_ifc_layers(pmmg_hip_ctx *ctx, int np, int ne, const int *tetv, const int *tet8,
+        int *mark,                    /* [ne] in / out                                         */
+        int ncolor, const int *weight,/* host [ncolor]                                         */
+        int *nelem,                   /* host [ncolor] in / out: negrp; -1 = not local         */
+        const int *nemin,             /* host [ncolor]                                         */
+        int *ptcolor, unsigned char *ptfront,   /* [np] in / out                               */
+        int nset, const int *set_pt, const int *set_color,  /* [nset]; set_color may be NULL   */
+        int nlayers,
+        int *layers_done, int *blocked,         /* host                                        */
+        int *moved);                  /* host [nlayers]: tetra re-marked per layer             */
+
+/* The DISTR branch of PMMG_part_getInterfaces (:1176-1211): part[k] = the rank
+ * of mark[k] among the colours present in a used tetra, counted in ascending
+ * order[colour] (host [ncolor]: the colour's place in the caller's packing
+ * order, the reference's (i + myrank) % nprocs loop); *ngrp (host) = the
+ * colours present.  part of an unused tetra is 0.  The MMG branch is the
+ * identity on indices and needs no call.  mark and part may be one array. */
+int pmmg_hip_remap_colors(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *tet8, const int *mark,
+                          int ncolor, const int *order, int *part, int *ngrp);
 
 /* ---- One group split over the GPUs of a node -------------
  * One process per GPU (ParMmg's MPI ranks; GPU = node-local rank,

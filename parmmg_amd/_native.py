@@ -155,6 +155,13 @@ HIP_API = {
                                       c_void_p, P(c_int), P(c_int)]),
     "pmmg_hip_gather_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "pmmg_hip_split_rounds": (c_int, [c_void_p]),
+    "pmmg_hip_ifc_seed": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                  c_void_p]),
+    "pmmg_hip_ifc_layers": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, P(c_int), P(c_int),
+                                    c_void_p]),
+    "pmmg_hip_remap_colors": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                      P(c_int)]),
     "pmmg_hip_memcpy_h2d": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "pmmg_hip_memcpy_d2h": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "pmmg_hip_locate_interp_rec": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -231,6 +238,8 @@ HOST_API = {
     "pmmg_host_free": (None, [c_void_p]),
     "pmmg_check_part_contiguity": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "pmmg_fix_contiguity_split": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "pmmg_part_move_interfaces": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                          c_void_p, c_int, c_void_p, P(c_int), P(c_int)]),
     "pmmg_split_grps": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, P(HostSplitResult)]),
     "pmmg_split_result_free": (None, [P(HostSplitResult)]),

@@ -595,6 +595,7 @@ int pmmg_hip_release_scratch(pmmg_hip_ctx *c) {
   c->graph_cache = GraphCache{};
   c->contig_cache = ContigCache{};
   c->split_cache = SplitCache{};
+  c->move_cache = MoveCache{};
   for (DevBuf *b : {&c->bvals2, &c->rs_hist, &c->rs_csum, &c->start_tab}) b->release();
   c->start_valid = false; // (the next call with a point map builds the start tables again)
   for (pmmg_hip_ctx *l : c->lanes) pmmg_hip_destroy(l);
@@ -875,6 +876,71 @@ int pmmg_hip_gather_rows(pmmg_hip_ctx *c, int64_t n, const int *src, int size, c
 }
 
 int pmmg_hip_split_rounds(pmmg_hip_ctx *c) { return c ? c->split_cache.rounds : -1; }
+
+// ---- interface displacement (pmmg_moveifc.hip)
+
+// the arguments the three calls share; fills *m
+static int ifc_args(pmmg_hip_ctx *c, const char *who, int np, int ne, const int *tetv, const int *tet8, const int *mark,
+                    int ncolor, const void *host, TetView *m) {
+  const TetArgs ta = tet_view(ne, tetv, nullptr, tet8, TET_NEED_TETV, m);
+  if (np < 0 || ne < 0 || ncolor < 1 || !host || ta == TET_MISSING || (ne > 0 && !mark)) {
+    set_err(c, "%s: invalid arguments (np=%d ne=%d ncolor=%d)", who, np, ne, ncolor);
+    return 0;
+  }
+  if (ta == TET_TOOMANY) {
+    set_err(c, "%s: %d tetra exceed the 4*k+i corner encoding (2^29)", who, ne);
+    return 0;
+  }
+  if ((ne > 0 && !aligned<16>(m->tetv)) || !aligned<4>(mark)) {
+    set_err(c, "%s: device tetra arrays must be 16-byte, every other int array 4-byte aligned", who);
+    return 0;
+  }
+  return 1;
+}
+
+int pmmg_hip_ifc_seed(pmmg_hip_ctx *c, int np, int ne, const int *tetv, const int *tet8, const int *mark, int ncolor,
+                      const int *weight, int *ptcolor, unsigned char *ptfront) {
+  if (!enter(c)) return 0;
+  TetView m;
+  if (!ifc_args(c, "ifc_seed", np, ne, tetv, tet8, mark, ncolor, weight, &m)) return 0;
+  if (np > 0 && (!ptcolor || !ptfront || !aligned<4>(ptcolor))) {
+    set_err(c, "ifc_seed: invalid arguments (ptcolor / ptfront NULL, or ptcolor not 4-byte aligned)");
+    return 0;
+  }
+  return pmmg_ifc_seed(c->stream, np, m, mark, ncolor, weight, ptcolor, ptfront, &c->move_cache, c->err, sizeof(c->err));
+}
+
+int pmmg_hip_ifc_layers(pmmg_hip_ctx *c, int np, int ne, const int *tetv, const int *tet8, int *mark, int ncolor,
+                        const int *weight, int *nelem, const int *nemin, int *ptcolor, unsigned char *ptfront, int nset,
+                        const int *set_pt, const int *set_color, int nlayers, int *layers_done, int *blocked,
+                        int *moved) {
+  if (!enter(c)) return 0;
+  TetView m;
+  if (!ifc_args(c, "ifc_layers", np, ne, tetv, tet8, mark, ncolor, weight, &m)) return 0;
+  if (!nelem || !nemin || !layers_done || !blocked || nlayers < 0 || (nlayers > 0 && !moved) || nset < 0 ||
+      (nset > 0 && !set_pt) || (np > 0 && (!ptcolor || !ptfront))) {
+    set_err(c, "ifc_layers: invalid arguments (nset=%d nlayers=%d, or a NULL array)", nset, nlayers);
+    return 0;
+  }
+  if (!aligned<4>(ptcolor) || !aligned<4>(set_pt) || !aligned<4>(set_color)) {
+    set_err(c, "ifc_layers: device tetra arrays must be 16-byte, every other int array 4-byte aligned");
+    return 0;
+  }
+  return pmmg_ifc_layers(c->stream, np, m, mark, ncolor, weight, nelem, nemin, ptcolor, ptfront, nset, set_pt,
+                         set_color, nlayers, layers_done, blocked, moved, &c->move_cache, c->err, sizeof(c->err));
+}
+
+int pmmg_hip_remap_colors(pmmg_hip_ctx *c, int ne, const int *tetv, const int *tet8, const int *mark, int ncolor,
+                          const int *order, int *part, int *ngrp) {
+  if (!enter(c)) return 0;
+  TetView m;
+  if (!ifc_args(c, "remap_colors", 0, ne, tetv, tet8, mark, ncolor, order, &m)) return 0;
+  if (!ngrp || (ne > 0 && !part) || !aligned<4>(part)) {
+    set_err(c, "remap_colors: invalid arguments (ngrp / part NULL, or part not 4-byte aligned)");
+    return 0;
+  }
+  return pmmg_ifc_remap(c->stream, m, mark, ncolor, order, part, ngrp, &c->move_cache, c->err, sizeof(c->err));
+}
 
 int pmmg_hip_build_boundary(pmmg_hip_ctx *c, int np, int ne, const int *tet8, const int *tetv, const int *adja,
                             const int *tref, int cap, int *nt, int *triv, int *adjt) {

@@ -391,6 +391,60 @@ int pmmg_fix_contiguity_split(pmmg_hip_ctx *ctx, int ne, const int *tetv, const 
 }
 
 
+/* ---------------------------------------------------------------- interface displacement */
+
+int pmmg_part_move_interfaces(pmmg_hip_ctx *ctx, int np, int ne, const int *tetv, const int *adja, const int *mark,
+                              int ncolor, const int *weight, const int *nelem_local, int nlayers, int *part_out,
+                              int *layers_done, int *blocked) {
+  if (!ctx) {
+    fprintf(stderr, "[parmmg_host] no HIP context: the interface displacement has no CPU fallback\n");
+    return 0;
+  }
+  if (np < 0 || ne < 0 || ncolor < 1 || nlayers < 0 || !weight || !nelem_local ||
+      (ne > 0 && (!tetv || !mark || !part_out)))
+    return 0;
+  int done = 0, blk = 0;
+  if (layers_done) *layers_done = 0;
+  if (blocked) *blocked = 0;
+  if (ne == 0) return 1;
+  int *nelem = (int *)malloc(sizeof(int) * (size_t)ncolor * 2), *moved = (int *)malloc(sizeof(int) * (size_t)(nlayers + 1));
+  void *d[3] = {NULL, NULL, NULL}, *color = NULL, *front = NULL;
+  int ok = nelem && moved;
+  if (ok) {
+    int *nemin = nelem + ncolor;
+    for (int g = 0; g < ncolor; g++) {
+      nelem[g] = nelem_local[g];
+      const int half = nelem[g] / 2 + 1;
+      nemin[g] = nelem[g] < 0 ? 0 : (half < 6 ? half : 6); /* MG_MIN(PMMG_REDISTR_NELEM_MIN, negrp/2+1) */
+    }
+    ok = contig_up(ctx, ne, tetv, adja, mark, d);
+    color = ok ? pmmg_hip_malloc(ctx, (int64_t)sizeof(int) * np) : NULL;
+    front = color ? pmmg_hip_malloc(ctx, np) : NULL;
+    ok = ok && color && front;
+    if (ok) ok = pmmg_hip_ifc_seed(ctx, np, ne, (const int *)d[0], NULL, (const int *)d[2], ncolor, weight, (int *)color,
+                                   (unsigned char *)front);
+    if (ok)
+      ok = pmmg_hip_ifc_layers(ctx, np, ne, (const int *)d[0], NULL, (int *)d[2], ncolor, weight, nelem, nemin,
+                               (int *)color, (unsigned char *)front, 0, NULL, NULL, nlayers, &done, &blk, moved);
+    if (ok && !blk) {
+      int64_t nmoved = 0;
+      int nmerged = 0, nstuck = 0;
+      ok = pmmg_hip_fix_contiguity(ctx, ne, (const int *)d[0], (const int *)d[1], NULL, (int *)d[2], ncolor, &nmoved,
+                                   &nmerged, &nstuck);
+    }
+    if (ok) ok = pmmg_hip_memcpy_d2h(ctx, part_out, d[2], (int64_t)sizeof(int) * ne);
+  }
+  if (ok && layers_done) *layers_done = done;
+  if (ok && blocked) *blocked = blk;
+  contig_free(ctx, d);
+  if (color) pmmg_hip_free(ctx, color);
+  if (front) pmmg_hip_free(ctx, front);
+  free(nelem);
+  free(moved);
+  return ok;
+}
+
+
 /* ---------------------------------------------------------------- group split */
 
 void pmmg_split_result_free(pmmg_split_result *r) {

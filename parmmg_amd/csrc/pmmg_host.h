@@ -157,6 +157,27 @@ int pmmg_check_part_contiguity(pmmg_hip_ctx *ctx, int ne, const int *tetv, const
  * include/parmmg_hip.h describes.  Returns 1, or 0 with part unchanged. */
 int pmmg_fix_contiguity_split(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *adja, int ngrp, int *part);
 
+/* ---- Interface displacement -------------------------------------------------
+ * PMMG_part_moveInterfaces (src/moveinterfaces_pmmg.c:1306-1467) of one rank
+ * on host arrays: the seed of PMMG_mark_interfacePoints, nlayers layers
+ * (parmesh->info.ifc_layers) and PMMG_fix_contiguity (:1446), through
+ * pmmg_hip_ifc_seed, pmmg_hip_ifc_layers and pmmg_hip_fix_contiguity
+ * (include/parmmg_hip.h, "Interface displacement": the definition and its two
+ * deviations).  mark[ne] holds colour indices in [0, ncolor), weight[ncolor]
+ * the priority map (mapgrp), nelem_local[ncolor] the tetra of every local
+ * colour and -1 for a colour of another rank; nemin is the reference's
+ * MG_MIN(PMMG_REDISTR_NELEM_MIN, negrp/2+1).  adja may be NULL (the fix then
+ * builds the links on the device).  Without communicator points: the exchange
+ * between two layers and PMMG_check_reachability stay with the caller.
+ * part_out[ne] takes the marks; *layers_done and *blocked (may be NULL) as
+ * pmmg_hip_ifc_layers leaves them: a blocked layer is not an error, the caller
+ * finishes it with the reference's loop.  The fix runs only when every layer
+ * was done.  Returns 1, or 0 with part_out unchanged (the reference's
+ * convention). */
+int pmmg_part_move_interfaces(pmmg_hip_ctx *ctx, int np, int ne, const int *tetv, const int *adja, const int *mark,
+                              int ncolor, const int *weight, const int *nelem_local, int nlayers, int *part_out,
+                              int *layers_done, int *blocked);
+
 /* ---- Group split ------------------------------------------------------------
  * PMMG_split_grps (src/grpsplit_pmmg.c:1464) on host arrays in the "row r =
  * entity r+1" layout, through pmmg_hip_split_groups and pmmg_hip_gather_rows:

@@ -482,6 +482,72 @@ class TransferContext:
         return dict(nmoved=nmoved.value, nmerged=nmerged.value, nstuck=nstuck.value,
                     passes=int(self.lib.pmmg_hip_contig_passes(self.h)))
 
+    # ------------------------------------------------------------------ interface displacement
+    def interface_points(self, npt, mark, weight, tetv=None, tet8=None):
+        """PMMG_mark_interfacePoints on the device (pmmg_hip_ifc_seed): tetv or
+        tet8 and mark [ne] are device arrays, weight [ncolor] a host array (c
+        beats d iff weight[c] < weight[d]).  Returns (ptcolor int32 [np],
+        ptfront uint8 [np]) as DeviceArrays."""
+        if not all(_is_dev(a) for a in (tetv, tet8, mark) if a is not None):
+            raise ValueError("interface_points takes device arrays")
+        weight = np.ascontiguousarray(weight, np.int32)
+        ne = int((tet8 if tet8 is not None else tetv).shape[0])
+        color, front = self.empty((int(npt),), np.int32), self.empty((int(npt),), np.uint8)
+        self._ck(self.lib.pmmg_hip_ifc_seed(self.h, int(npt), ne, _p(tetv), _p(tet8), _p(mark), weight.size, _p(weight),
+                                            _p(color), _p(front)), "ifc_seed")
+        return color, front
+
+    def move_interfaces(self, npt, mark, weight, nelem, tetv=None, tet8=None, adja=None, ptcolor=None, ptfront=None,
+                        nlayers=2, set_pt=None, set_color=None, nemin=None, fix=True):
+        """The layer loop of PMMG_part_moveInterfaces on the device
+        (pmmg_hip_ifc_layers), then PMMG_fix_contiguity when fix is true and no
+        layer was blocked.  mark (device int32 [ne]) is changed in place.
+        weight, nelem (-1: a colour of another rank) are host arrays [ncolor];
+        nemin None: the reference's MG_MIN(6, nelem / 2 + 1).  ptcolor /
+        ptfront: the state of interface_points or of an earlier call, changed
+        in place (None: seeded here).  set_pt / set_color: device int32 arrays
+        of points made front before every layer and their colours before the
+        first.  Returns dict(layers_done, blocked, moved [nlayers], nelem,
+        ptcolor, ptfront, fix = fix_contiguity's dict or None)."""
+        given = [a for a in (tetv, tet8, adja, mark, ptcolor, ptfront, set_pt, set_color) if a is not None]
+        if not all(_is_dev(a) for a in given):
+            raise ValueError("move_interfaces takes device arrays")
+        weight = np.ascontiguousarray(weight, np.int32)
+        nelem = np.array(nelem, np.int32)
+        if nemin is None:
+            nemin = np.where(nelem >= 0, np.minimum(6, nelem // 2 + 1), 0)
+        nemin = np.ascontiguousarray(nemin, np.int32)
+        if ptcolor is None:
+            ptcolor, ptfront = self.interface_points(npt, mark, weight, tetv=tetv, tet8=tet8)
+        ne = int((tet8 if tet8 is not None else tetv).shape[0])
+        nset = 0 if set_pt is None else int(set_pt.shape[0])
+        moved = np.zeros(max(1, int(nlayers)), np.int32)
+        done, blocked = ctypes.c_int(0), ctypes.c_int(0)
+        self._ck(self.lib.pmmg_hip_ifc_layers(self.h, int(npt), ne, _p(tetv), _p(tet8), _p(mark), weight.size, _p(weight),
+                                              _p(nelem), _p(nemin), _p(ptcolor), _p(ptfront), nset, _p(set_pt),
+                                              _p(set_color), int(nlayers), ctypes.byref(done), ctypes.byref(blocked),
+                                              _p(moved)), "ifc_layers")
+        fixed = None
+        if fix and not blocked.value:
+            fixed = self.fix_contiguity(tetv, mark, weight.size, adja=adja, tet8=tet8)
+        return dict(layers_done=done.value, blocked=blocked.value, moved=moved[:int(nlayers)], nelem=nelem,
+                    ptcolor=ptcolor, ptfront=ptfront, fix=fixed)
+
+    def remap_colors(self, mark, ncolor, order=None, tetv=None, tet8=None, part=None):
+        """The packing of PMMG_part_getInterfaces (pmmg_hip_remap_colors): the
+        colours present among the used tetra numbered 0, 1, ... in ascending
+        order[colour] (None: the colours' own order).  Returns (part, ngrp);
+        part: the device array to fill, or None for a new one."""
+        if not all(_is_dev(a) for a in (tetv, tet8, mark, part) if a is not None):
+            raise ValueError("remap_colors takes device arrays")
+        order = np.ascontiguousarray(np.arange(int(ncolor)) if order is None else order, np.int32)
+        ne = int((tet8 if tet8 is not None else tetv).shape[0])
+        part = self.empty((ne,), np.int32) if part is None else part
+        ngrp = ctypes.c_int(0)
+        self._ck(self.lib.pmmg_hip_remap_colors(self.h, ne, _p(tetv), _p(tet8), _p(mark), int(ncolor), _p(order),
+                                                _p(part), ctypes.byref(ngrp)), "remap_colors")
+        return part, ngrp.value
+
     # ------------------------------------------------------------------ group split
     def split_groups(self, npt, part, ngrp, tetv=None, adja=None, tet8=None, node_pos=None, face_old=None, nnode0=0,
                      nface0=0, caps=None, want=("new_tet", "tet8_out")):
