@@ -730,6 +730,96 @@ int pmmg_hip_gather_rows(pmmg_hip_ctx *ctx, int64_t n, const int *src /*1-based*
  * that met at one vertex; tools/split_groups_time.py); -1 without a context. */
 int pmmg_hip_split_rounds(pmmg_hip_ctx *ctx);
 
+/* ---- Group merge: the groups of a rank joined into one mesh ----------------
+ * The inverse of the split, and the first statement of PMMG_split_n2mGrps
+ * before every redistribution: PMMG_merge_grps steps 0-4
+ * (src/mergemesh_pmmg.c:1004-1043; PMMG_mergeGrps_interfacePoints :433-469
+ * with _addGrpJ :303-422, PMMG_mergeGrpJinI_internalPoints :480-571,
+ * _interfaceTetra :584-682, _internalTetra :695-751, PMMG_set_color_tetra,
+ * src/moveinterfaces_pmmg.c:119-134).  The reference's loop is sequential; what
+ * it leaves in group 0 and in the two intvalues arrays is a function of its
+ * inputs, stated here and computed on the device.  Device pointers unless
+ * marked host, synchronous, main stream only, 1-based ids.
+ *   Input.  The groups concatenated in group order, as pmmg_hip_split_groups
+ *     writes them: count[g] = {ne, np, nface, nnode}, tetra rows with ids local
+ *     to their group (tet8 records when non-NULL, else tetv; links not read),
+ *     the node and face lists.  e is an entry's index in the concatenated node
+ *     (or face) list: ascending e is ascending (group, entry).  nnode / nface
+ *     are int_node_comm->nitem / int_face_comm->nitem.
+ *   Points.  A point of group 0 keeps its id.  For a group g >= 1, a point's
+ *     entry is the first entry of g's node list that names it (later ones are
+ *     skipped, :346) and its position that entry's index2.  Every entry of
+ *     group 0 holds its position (:452-459).  A listed point of g >= 1 whose
+ *     position group 0 holds takes group 0's id there (its index1).  The
+ *     other listed positions each become one new point, numbered np_0 + 1,
+ *     np_0 + 2, ... in ascending e of the position's lowest entry (step 1,
+ *     over all groups); every point listed at the position takes that id.
+ *     Then, group by group for g = 1, 2, ..., the points of g that no entry
+ *     names are numbered in ascending id (step 2).  new_pt[i] is the merged id
+ *     of concatenated point i (pptJ->tmp), src_pt[q - 1] the 1-based row, in the
+ *     concatenated points, of the point that made merged point q: its own row
+ *     for group 0, the lowest entry's point for a created one.
+ *   node_val[p] is int_node_comm->intvalues[p] after step 4: 0 where nobody
+ *     holds p; else the merged id of the point at p, negated once for every
+ *     further group that holds p (:400-401): the sign is (-1)^(holders - 1).
+ *   Tetra.  Group 0's tetra keep their ids; group g's get the ids from
+ *     ne_0 + ... + ne_(g-1) + 1 on: first g's interface tetra (those named by
+ *     an entry of g's face list, iel = index1 / 12) in order of their first
+ *     entry, then g's other tetra in ascending id.  tetv_out holds the
+ *     vertices renamed through new_pt, corner order kept; new_tet[k] the
+ *     merged id of concatenated tetra k (ptJ->flag), src_tet[m - 1] the 1-based
+ *     concatenated row of merged tetra m.  mark_out[m - 1] = color[g] of the
+ *     tetra's group (PMMG_GRPSPL_DISTR_TARGET).
+ *   face_val[q] is int_face_comm->intvalues[q] after step 4: 0 where no entry
+ *     names q; else the value of q's lowest entry, index1 as it stands for an
+ *     entry of group 0 (:1008-1014) and 12 * merged tetra + index1 % 12 for a
+ *     group g >= 1, negated by every later entry of a group g >= 1 with that
+ *     position (:629-631, :657-658).
+ * Preconditions, the reference's own: every group packed (no unused tetra or
+ * point, group 0's free lists in order); within one group a node position
+ * names one point and a face position appears once.  The last two are not
+ * checked: the outputs then still are ids in range.  With one group the
+ * reference returns before it allocates the intvalues (:990); the statement
+ * above is applied all the same.
+ * Out of scope, gathered by the caller through src_pt / src_tet
+ * (pmmg_hip_gather_rows, pmmg_hip_gather_rows_i32): xtetra / xpoint records,
+ * ref, qual, tags, the solution rows; reallocation;
+ * PMMG_mergeGrps_communicators and PMMG_updateTag, which take node_val /
+ * face_val as the two intvalues; the adjacency, which the reference frees
+ * (:987): pmmg_hip_build_adjacency on tetv_out rebuilds it.
+ * Returns 0 (message in pmmg_hip_last_error) with nothing written to any
+ * device output when a vertex id lies outside [1, np_g], a node index1
+ * outside [1, np_g], a node index2 outside [0, nnode), a face index1 / 12
+ * outside [1, ne_g], a face index2 outside [0, nface), the tetra of all
+ * groups reach 178956970 (12 * ie + 11 must fit an int, the reference's limit
+ * too), the points, the entries of a list or the positions reach 2^29, or an
+ * array is misaligned (tetv / tet8 / tetv_out 16 bytes, every other 4).
+ * Returns 0 as well when pt_cap is smaller than the merged points: *np_out and
+ * *ne_out are filled and no device output is written (call with pt_cap = 0 to
+ * size).  ngrp == 1, empty groups and no tetra at all are valid.  Scratch
+ * lives in the context (pmmg_hip_release_scratch).  Two calls on the same
+ * inputs give byte-identical outputs. */
+int pmmg_hip_merge_groups(pmmg_hip_ctx *ctx, int ngrp, const pmmg_hip_split_count *count /*host*/,
+        const int *tetv, const int *tet8,            /* [sum ne] rows, group-local ids; tet8 wins, links not read */
+        const int *node_idx1, const int *node_idx2,  /* [sum nnode] */
+        const int *face_idx1, const int *face_idx2,  /* [sum nface] */
+        int nnode, int nface,                        /* the two int_*_comm->nitem */
+        const int *color,                            /* host [ngrp] or NULL (then mark_out must be NULL) */
+        int64_t pt_cap,
+        int *new_pt,   /* [sum np] merged id of every input point (pptJ->tmp)            */
+        int *new_tet,  /* [sum ne] merged id of every input tetra (ptJ->flag), may be NULL */
+        int *src_pt,   /* [pt_cap] 1-based row in the concatenated points of every merged point */
+        int *src_tet,  /* [sum ne] 1-based row in the concatenated tetra of every merged tetra  */
+        int *tetv_out, int *mark_out,                /* [4 sum ne], [sum ne]; each may be NULL */
+        int *node_val, int *face_val,                /* [nnode], [nface]; each may be NULL */
+        int *np_out, int *ne_out);                   /* host */
+
+/* pmmg_hip_gather_rows for rows of `size` ints: the ref / mark rows of the
+ * merged tetra through src_tet.  src, in, out 4-byte aligned; every src[r] must
+ * name a row of `in` (not checked).  Synchronous. */
+int pmmg_hip_gather_rows_i32(pmmg_hip_ctx *ctx, int64_t n, const int *src /*1-based*/, int size,
+                             const int *in, int *out);
+
 /* ---- Interface displacement: move the group fronts by layers ----------------
  * PMMG_mark_interfacePoints and the layer loop of PMMG_part_moveInterfaces
  * (src/moveinterfaces_pmmg.c:1052-1090, :1366-1439; PMMG_REDISTRIBUTION_

@@ -91,6 +91,16 @@ class HostSplitResult(ctypes.Structure):
     ]
 
 
+class HostMergeResult(ctypes.Structure):
+    """``pmmg_merge_result`` of csrc/pmmg_host.h."""
+
+    _fields_ = [
+        ("np", c_int), ("ne", c_int), ("new_pt", P(c_int)), ("src_pt", P(c_int)), ("new_tet", P(c_int)),
+        ("src_tet", P(c_int)), ("tetv", P(c_int)), ("mark", P(c_int)), ("tref", P(c_int)), ("xyz", P(c_double)),
+        ("met", P(c_double)), ("met_size", c_int), ("node_val", P(c_int)), ("face_val", P(c_int)),
+    ]
+
+
 class HipGroup(ctypes.Structure):
     """``pmmg_hip_group`` of include/parmmg_hip.h (device pointers)."""
 
@@ -155,6 +165,10 @@ HIP_API = {
                                       c_void_p, P(c_int), P(c_int)]),
     "pmmg_hip_gather_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "pmmg_hip_split_rounds": (c_int, [c_void_p]),
+    "pmmg_hip_merge_groups": (c_int, [c_void_p, c_int, P(HipSplitCount), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, P(c_int), P(c_int)]),
+    "pmmg_hip_gather_rows_i32": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "pmmg_hip_ifc_seed": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                   c_void_p]),
     "pmmg_hip_ifc_layers": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
@@ -243,6 +257,9 @@ HOST_API = {
     "pmmg_split_grps": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, P(HostSplitResult)]),
     "pmmg_split_result_free": (None, [P(HostSplitResult)]),
+    "pmmg_merge_grps": (c_int, [c_void_p, c_int, P(HipSplitCount), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, P(HostMergeResult)]),
+    "pmmg_merge_result_free": (None, [P(HostMergeResult)]),
     "pmmg_max_tet_extent": (c_double, [c_int, c_void_p, c_int, c_void_p]),
     "pmmg_shard_mark": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                                 c_void_p, P(c_int64)]),

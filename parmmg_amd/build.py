@@ -64,14 +64,16 @@ def build_hip(force: bool = False) -> str:
     contig = os.path.join(CSRC, "pmmg_contig.hip")
     split = os.path.join(CSRC, "pmmg_split.hip")
     moveifc = os.path.join(CSRC, "pmmg_moveifc.hip")
-    deps = [src, snap, qual, mstats, graph, contig, split, moveifc, os.path.join(INC, "parmmg_hip.h"), __file__] + [
+    merge = os.path.join(CSRC, "pmmg_merge.hip")
+    deps = [src, snap, qual, mstats, graph, contig, split, moveifc, merge, os.path.join(INC, "parmmg_hip.h"), __file__] + [
         os.path.join(CSRC, h) for h in ("pmmg_device.hpp", "pmmg_prep.hpp", "pmmg_vol.hpp", "pmmg_bdy.hpp",
                                         "pmmg_fallback.hpp", "pmmg_snapshot.hpp", "pmmg_quality.hpp",
                                         "pmmg_meshstats.hpp", "pmmg_graph.hpp", "pmmg_sort.hpp", "pmmg_comm.hpp",
                                         "pmmg_devbuf.hpp", "pmmg_devutil.hpp", "pmmg_ctx.hpp", "pmmg_xfer.hpp",
                                         "pmmg_carry.hpp", "pmmg_call.hpp", "pmmg_groups.hpp", "pmmg_contig.hpp",
                                         "pmmg_contig_decide.hpp", "pmmg_tetview.hpp", "pmmg_blockscan.hpp",
-                                        "pmmg_split.hpp", "pmmg_moveifc.hpp", "pmmg_moveifc_decide.hpp")]
+                                        "pmmg_split.hpp", "pmmg_moveifc.hpp", "pmmg_moveifc_decide.hpp",
+                                        "pmmg_merge.hpp", "pmmg_merge_tables.hpp")]
     if force or _stale(out, deps):
         # max-memory-clause scheduling: the gathers of a step issued as clauses
         # (volume kernel -4.6 % at cfg4, same registers; profiles/r02e/sweep_sched_strategy.txt)
@@ -79,7 +81,7 @@ def build_hip(force: bool = False) -> str:
               "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
               # (r05: flowing off a lambda that a `return 0` made non-void is undefined: a host segfault)
               "-Werror=return-type", f"-I{INC}", "-o", out, src, snap, qual, mstats, graph, contig,
-              split, moveifc])
+              split, moveifc, merge])
     return out
 
 

@@ -26,6 +26,7 @@
 #include "pmmg_contig.hpp"
 #include "pmmg_split.hpp"
 #include "pmmg_moveifc.hpp"
+#include "pmmg_merge.hpp"
 
 using namespace pmmg;
 
@@ -66,6 +67,7 @@ struct CtxBufs {
   ContigCache contig_cache; // pmmg_hip_part_subgroups / pmmg_hip_fix_contiguity: labels, the table (pmmg_contig.hip)
   SplitCache split_cache; // pmmg_hip_split_groups: the new order, first uses, masks and prefixes (pmmg_split.hip)
   MoveCache move_cache; // pmmg_hip_ifc_seed / _ifc_layers / _remap_colors: keys, copies of a layer (pmmg_moveifc.hip)
+  MergeCache merge_cache; // pmmg_hip_merge_groups: the tables, lowest entries, counts and prefixes (pmmg_merge.hip)
   struct Kept { // a carry-over slot (see pmmg_hip_ctx::carry_slot)
     DevBuf xyz, met;
     std::vector<DevBuf> f;

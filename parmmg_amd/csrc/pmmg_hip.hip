@@ -596,6 +596,7 @@ int pmmg_hip_release_scratch(pmmg_hip_ctx *c) {
   c->contig_cache = ContigCache{};
   c->split_cache = SplitCache{};
   c->move_cache = MoveCache{};
+  c->merge_cache = MergeCache{};
   for (DevBuf *b : {&c->bvals2, &c->rs_hist, &c->rs_csum, &c->start_tab}) b->release();
   c->start_valid = false; // (the next call with a point map builds the start tables again)
   for (pmmg_hip_ctx *l : c->lanes) pmmg_hip_destroy(l);
@@ -876,6 +877,67 @@ int pmmg_hip_gather_rows(pmmg_hip_ctx *c, int64_t n, const int *src, int size, c
 }
 
 int pmmg_hip_split_rounds(pmmg_hip_ctx *c) { return c ? c->split_cache.rounds : -1; }
+
+// ---- group merge (pmmg_merge.hip)
+
+int pmmg_hip_merge_groups(pmmg_hip_ctx *c, int ngrp, const pmmg_hip_split_count *count, const int *tetv, const int *tet8,
+                          const int *node_idx1, const int *node_idx2, const int *face_idx1, const int *face_idx2,
+                          int nnode, int nface, const int *color, int64_t pt_cap, int *new_pt, int *new_tet, int *src_pt,
+                          int *src_tet, int *tetv_out, int *mark_out, int *node_val, int *face_val, int *np_out,
+                          int *ne_out) {
+  if (!enter(c)) return 0;
+  if (ngrp < 1 || !count || nnode < 0 || nface < 0 || pt_cap < 0 || !np_out || !ne_out || (!color && mark_out)) {
+    set_err(c, "merge_groups: invalid arguments (ngrp=%d nnode=%d nface=%d pt_cap=%lld, a NULL count or counter, or "
+               "mark_out without color)", ngrp, nnode, nface, (long long)pt_cap);
+    return 0;
+  }
+  if (nnode >= kTetMax || nface >= kTetMax) {
+    set_err(c, "merge_groups: %d node or %d face positions reach 2^29", nnode, nface);
+    return 0;
+  }
+  int64_t tot[4] = {0, 0, 0, 0};
+  for (int g = 0; g < ngrp; g++) {
+    tot[0] += count[g].ne > 0;
+    tot[1] += count[g].np > 0;
+    tot[2] += count[g].nface > 0;
+    tot[3] += count[g].nnode > 0;
+  }
+  if ((tot[0] && ((!tetv && !tet8) || !src_tet)) || (tot[1] && !new_pt) || (tot[2] && (!face_idx1 || !face_idx2)) ||
+      (tot[3] && (!node_idx1 || !node_idx2))) {
+    set_err(c, "merge_groups: invalid arguments (an array with entries is NULL)");
+    return 0;
+  }
+  const int *rows = tet8 ? tet8 : tetv;
+  if (!aligned<16>(rows) || !aligned<16>(tetv_out)) {
+    set_err(c, "merge_groups: device tetra arrays (in and out) must be 16-byte aligned");
+    return 0;
+  }
+  for (const void *p : {(const void *)node_idx1, (const void *)node_idx2, (const void *)face_idx1,
+                        (const void *)face_idx2, (const void *)new_pt, (const void *)new_tet, (const void *)src_pt,
+                        (const void *)src_tet, (const void *)mark_out, (const void *)node_val, (const void *)face_val})
+    if (!aligned<4>(p)) {
+      set_err(c, "merge_groups: the lists, the maps and the values must be 4-byte aligned");
+      return 0;
+    }
+  const MergeArgs a{ngrp, count, rows, tet8 ? 2 : 1, node_idx1, node_idx2, face_idx1, face_idx2, nnode, nface, color,
+                    pt_cap, new_pt, new_tet, src_pt, src_tet, tetv_out, mark_out, node_val, face_val, np_out, ne_out};
+  return pmmg_merge_groups(c->stream, a, &c->merge_cache, c->err, sizeof(c->err));
+}
+
+int pmmg_hip_gather_rows_i32(pmmg_hip_ctx *c, int64_t n, const int *src, int size, const int *in, int *out) {
+  if (!enter(c)) return 0;
+  if (n < 0 || size < 1 || (n > 0 && (!src || !in || !out))) {
+    set_err(c, "gather_rows_i32: invalid arguments (n=%lld size=%d)", (long long)n, size);
+    return 0;
+  }
+  if (!aligned<4>(src) || !aligned<4>(in) || !aligned<4>(out)) {
+    set_err(c, "gather_rows_i32: src, in and out must be 4-byte aligned");
+    return 0;
+  }
+  if (!pmmg_merge_gather_i32(c->stream, n, src, size, in, out, c->err, sizeof(c->err))) return 0;
+  HIPCK(c, hipStreamSynchronize(c->stream));
+  return 1;
+}
 
 // ---- interface displacement (pmmg_moveifc.hip)
 

@@ -595,3 +595,108 @@ int pmmg_split_grps(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne, const 
   if (!ok) pmmg_split_result_free(out);
   return ok;
 }
+
+/* ---------------------------------------------------------------- group merge */
+
+void pmmg_merge_result_free(pmmg_merge_result *r) {
+  if (!r) return;
+  void *p[] = {r->new_pt, r->src_pt, r->new_tet, r->src_tet, r->tetv, r->mark, r->tref, r->xyz, r->met, r->node_val,
+               r->face_val};
+  for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); i++) free(p[i]);
+  memset(r, 0, sizeof(*r));
+}
+
+int pmmg_merge_grps(pmmg_hip_ctx *ctx, int ngrp, const pmmg_hip_split_count *count, const int *tetv,
+                    const int *node_idx1, const int *node_idx2, const int *face_idx1, const int *face_idx2, int nnode,
+                    int nface, const int *color, const double *xyz, int met_size, const double *met, const int *tref,
+                    pmmg_merge_result *out) {
+  if (!ctx) {
+    fprintf(stderr, "[parmmg_host] no HIP context: the group merge has no CPU fallback\n");
+    return 0;
+  }
+  if (!out) return 0;
+  memset(out, 0, sizeof(*out));
+  if (ngrp < 1 || !count || nnode < 0 || nface < 0) return 0;
+  int64_t nt = 0, npt = 0, nfe = 0, nne = 0;
+  for (int g = 0; g < ngrp; g++) {
+    if (count[g].ne < 0 || count[g].np < 0 || count[g].nface < 0 || count[g].nnode < 0) return 0;
+    nt += count[g].ne;
+    npt += count[g].np;
+    nfe += count[g].nface;
+    nne += count[g].nnode;
+  }
+  if ((nt > 0 && !tetv) || (npt > 0 && !xyz) || (nfe > 0 && (!face_idx1 || !face_idx2)) ||
+      (nne > 0 && (!node_idx1 || !node_idx2)))
+    return 0;
+  if (!met) met_size = 0;
+  const int64_t i4 = (int64_t)sizeof(int), d8 = (int64_t)sizeof(double);
+  enum { D_TETV, D_N1, D_N2, D_F1, D_F2, D_XYZ, D_MET, D_TREF, D_NEWP, D_NEWT, D_SRCP, D_SRCT, D_TV, D_MARK, D_NVAL,
+         D_FVAL, D_ROWS, D_TROW, D_COUNT };
+  void *d[D_COUNT] = {NULL};
+  int ok = 1;
+#define UP(slot, src, bytes)                                                                   \
+  do {                                                                                         \
+    if (ok && (src) && (bytes) > 0) {                                                          \
+      d[slot] = pmmg_hip_malloc(ctx, (int64_t)(bytes));                                        \
+      ok = d[slot] != NULL && pmmg_hip_memcpy_h2d(ctx, d[slot], (src), (int64_t)(bytes));      \
+    }                                                                                          \
+  } while (0)
+#define ROOM(slot, bytes)                                                                      \
+  do {                                                                                         \
+    if (ok) ok = (d[slot] = pmmg_hip_malloc(ctx, (int64_t)(bytes) > 0 ? (int64_t)(bytes) : 16)) != NULL; \
+  } while (0)
+  UP(D_TETV, tetv, i4 * 4 * nt);
+  UP(D_N1, node_idx1, i4 * nne);
+  UP(D_N2, node_idx2, i4 * nne);
+  UP(D_F1, face_idx1, i4 * nfe);
+  UP(D_F2, face_idx2, i4 * nfe);
+  ROOM(D_NEWP, i4 * npt);
+  ROOM(D_NEWT, i4 * nt);
+  ROOM(D_SRCP, i4 * npt); /* (the merged points are at most the groups') */
+  ROOM(D_SRCT, i4 * nt);
+  ROOM(D_TV, i4 * 4 * nt);
+  if (color) ROOM(D_MARK, i4 * nt);
+  ROOM(D_NVAL, i4 * nnode);
+  ROOM(D_FVAL, i4 * nface);
+  if (ok)
+    ok = pmmg_hip_merge_groups(ctx, ngrp, count, (const int *)d[D_TETV], NULL, (const int *)d[D_N1],
+                               (const int *)d[D_N2], (const int *)d[D_F1], (const int *)d[D_F2], nnode, nface, color,
+                               npt, (int *)d[D_NEWP], (int *)d[D_NEWT], (int *)d[D_SRCP], (int *)d[D_SRCT],
+                               (int *)d[D_TV], (int *)d[D_MARK], (int *)d[D_NVAL], (int *)d[D_FVAL], &out->np, &out->ne);
+  /* the point rows through src_pt and the references through src_tet, through one device block */
+  const int width = met_size > 3 ? met_size : 3;
+  UP(D_XYZ, xyz, d8 * 3 * npt);
+  ROOM(D_ROWS, d8 * width * (ok ? out->np : 0));
+  if (ok) ok = pmmg_hip_gather_rows(ctx, out->np, (const int *)d[D_SRCP], 3, (const double *)d[D_XYZ], (double *)d[D_ROWS]);
+  if (ok) ok = (out->xyz = (double *)split_down(ctx, d[D_ROWS], d8 * 3 * out->np)) != NULL;
+  if (met_size) {
+    UP(D_MET, met, d8 * met_size * npt);
+    if (ok)
+      ok = pmmg_hip_gather_rows(ctx, out->np, (const int *)d[D_SRCP], met_size, (const double *)d[D_MET],
+                                (double *)d[D_ROWS]);
+    if (ok) ok = (out->met = (double *)split_down(ctx, d[D_ROWS], d8 * met_size * out->np)) != NULL;
+  }
+  out->met_size = met_size;
+  if (tref) {
+    UP(D_TREF, tref, i4 * nt);
+    ROOM(D_TROW, i4 * nt);
+    if (ok) ok = pmmg_hip_gather_rows_i32(ctx, nt, (const int *)d[D_SRCT], 1, (const int *)d[D_TREF], (int *)d[D_TROW]);
+    if (ok) ok = (out->tref = (int *)split_down(ctx, d[D_TROW], i4 * nt)) != NULL;
+  }
+#undef UP
+#undef ROOM
+  if (ok) {
+    ok = (out->new_pt = (int *)split_down(ctx, d[D_NEWP], i4 * npt)) != NULL &&
+         (out->src_pt = (int *)split_down(ctx, d[D_SRCP], i4 * out->np)) != NULL &&
+         (out->new_tet = (int *)split_down(ctx, d[D_NEWT], i4 * nt)) != NULL &&
+         (out->src_tet = (int *)split_down(ctx, d[D_SRCT], i4 * nt)) != NULL &&
+         (out->tetv = (int *)split_down(ctx, d[D_TV], i4 * 4 * nt)) != NULL &&
+         (!color || (out->mark = (int *)split_down(ctx, d[D_MARK], i4 * nt)) != NULL) &&
+         (out->node_val = (int *)split_down(ctx, d[D_NVAL], i4 * nnode)) != NULL &&
+         (out->face_val = (int *)split_down(ctx, d[D_FVAL], i4 * nface)) != NULL;
+  }
+  for (int i = 0; i < D_COUNT; i++)
+    if (d[i]) pmmg_hip_free(ctx, d[i]);
+  if (!ok) pmmg_merge_result_free(out);
+  return ok;
+}

@@ -211,6 +211,37 @@ int pmmg_split_grps(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne, const 
                     pmmg_split_result *out);
 void pmmg_split_result_free(pmmg_split_result *r);
 
+/* ---- Group merge ------------------------------------------------------------
+ * PMMG_merge_grps steps 0-4 (src/mergemesh_pmmg.c:967-1043) on host arrays,
+ * through pmmg_hip_merge_groups, pmmg_hip_gather_rows and
+ * pmmg_hip_gather_rows_i32: the groups concatenated in group order, as
+ * pmmg_split_grps returns them (count[ngrp], tetv [4*sum ne] with group-local
+ * ids, the two lists, xyz [3*sum np], the metric (met NULL: none), tref
+ * [sum ne] (NULL: none)) go up; the merge runs on the device; the point rows
+ * are gathered there through src_pt and tref through src_tet; everything comes
+ * back in arrays this call allocates.  color [ngrp] (NULL: no mark) is the
+ * mark every group's tetra get.  node_val [nnode] / face_val [nface] are the
+ * two intvalues that the reference's own step 5
+ * (PMMG_mergeGrps_communicators) takes.  What the arrays hold is stated in
+ * include/parmmg_hip.h.  Release them with pmmg_merge_result_free.  Returns 1,
+ * or 0 as the reference does, with *out zeroed (the reason in
+ * pmmg_hip_last_error). */
+typedef struct {
+  int np, ne;                         /* the merged mesh */
+  int *new_pt, *src_pt;               /* [sum np], [np] */
+  int *new_tet, *src_tet;             /* [ne] */
+  int *tetv, *mark, *tref;            /* [4*ne], [ne] (NULL without color), [ne] (NULL without tref) */
+  double *xyz, *met;                  /* [3*np], [met_size*np] (NULL without a metric) */
+  int met_size;
+  int *node_val, *face_val;           /* [nnode], [nface] */
+} pmmg_merge_result;
+
+int pmmg_merge_grps(pmmg_hip_ctx *ctx, int ngrp, const pmmg_hip_split_count *count, const int *tetv,
+                    const int *node_idx1, const int *node_idx2, const int *face_idx1, const int *face_idx2, int nnode,
+                    int nface, const int *color, const double *xyz, int met_size, const double *met, const int *tref,
+                    pmmg_merge_result *out);
+void pmmg_merge_result_free(pmmg_merge_result *r);
+
 /* ---- halo shards of a background group (pmmg_shard.c) ----
  * All arrays in the "row r = entity r+1" layout of parmmg_hip.h. */
 

@@ -660,6 +660,83 @@ class TransferContext:
             groups.append(d)
         return groups, [g_xyz] + ([] if g_met is None else [g_met]) + g_f
 
+    # ------------------------------------------------------------------ group merge
+    def merge_groups(self, split_or_arrays, color=None, nnode=None, nface=None, pt_cap=None,
+                     want=("new_tet", "tetv_out", "node_val", "face_val")):
+        """PMMG_merge_grps steps 0-4 on the device (pmmg_hip_merge_groups):
+        device arrays in, device arrays out.  split_or_arrays: the dict that
+        split_groups returns, or one with count [ngrp, 4] (host), tet8_out or
+        tetv_out, face_idx1, face_idx2, node_idx1, node_idx2 (device, groups
+        concatenated), and nnode_end / nface_end unless nnode / nface (the two
+        nitem) are given.  color [ngrp] (host) or None: the mark of every
+        group's tetra (mark_out).  want: which of new_tet, tetv_out, node_val,
+        face_val to write.  pt_cap None: the groups' points, which the merged
+        points never exceed.  Returns a dict: np, ne, new_pt [sum np], src_pt
+        [np], src_tet [ne], mark_out (with color) and the arrays of `want`."""
+        a = split_or_arrays
+        unknown = set(want) - {"new_tet", "tetv_out", "node_val", "face_val"}
+        if unknown:
+            raise ValueError(f"merge_groups: unknown outputs {sorted(unknown)}")
+        tet8, tetv = a.get("tet8_out"), a.get("tetv_out")
+        if tet8 is not None:
+            tetv = None
+        lists = [a["node_idx1"], a["node_idx2"], a["face_idx1"], a["face_idx2"]]
+        if not all(_is_dev(x) for x in lists + [tet8, tetv] if x is not None):
+            raise ValueError("merge_groups takes device arrays")
+        c = np.ascontiguousarray(a["count"], np.int32).reshape(-1, 4)
+        ngrp = int(c.shape[0])
+        count = (HipSplitCount * max(1, ngrp))(*[HipSplitCount(*[int(v) for v in r]) for r in c])
+        tne, tnp = int(c[:, 0].sum()), int(c[:, 1].sum())
+        nnode = int(a["nnode_end"] if nnode is None else nnode)
+        nface = int(a["nface_end"] if nface is None else nface)
+        cap = tnp if pt_cap is None else int(pt_cap)
+        color = None if color is None else np.ascontiguousarray(color, np.int32)
+        if color is not None and color.shape != (ngrp,):
+            raise ValueError("merge_groups: color must hold one entry per group")
+        out = dict(new_pt=self.empty((tnp,), np.int32), src_pt=self.empty((cap,), np.int32),
+                   src_tet=self.empty((tne,), np.int32),
+                   new_tet=self.empty((tne,), np.int32) if "new_tet" in want else None,
+                   tetv_out=self.empty((tne, 4), np.int32) if "tetv_out" in want else None,
+                   mark_out=self.empty((tne,), np.int32) if color is not None else None,
+                   node_val=self.empty((nnode,), np.int32) if "node_val" in want else None,
+                   face_val=self.empty((nface,), np.int32) if "face_val" in want else None)
+        npo, neo = ctypes.c_int(0), ctypes.c_int(0)
+        ok = self.lib.pmmg_hip_merge_groups(
+            self.h, ngrp, count, _p(tetv), _p(tet8), *[_p(x) for x in lists], nnode, nface, _p(color), cap,
+            _p(out["new_pt"]), _p(out["new_tet"]), _p(out["src_pt"]), _p(out["src_tet"]), _p(out["tetv_out"]),
+            _p(out["mark_out"]), _p(out["node_val"]), _p(out["face_val"]), ctypes.byref(npo), ctypes.byref(neo))
+        if not ok:
+            for x in out.values():
+                if x is not None:
+                    x.free()
+            err = RuntimeError(f"merge_groups failed: {self.error()}")
+            err.np, err.ne = npo.value, neo.value  # (filled when only pt_cap was short)
+            raise err
+        out["src_pt"].shape, out["src_pt"].nbytes = (npo.value,), 4 * npo.value  # (the cap may exceed the points)
+        out.update(np=npo.value, ne=neo.value)
+        return out
+
+    def gather_rows_i32(self, src, rows, out=None):
+        """gather_rows for int32 rows (pmmg_hip_gather_rows_i32): the ref /
+        mark rows of the merged tetra through src_tet.  rows int32 [m] or
+        [m, size]; returns the DeviceArray [n] or [n, size] (out, when given)."""
+        if not (_is_dev(src) and _is_dev(rows) and (out is None or _is_dev(out))):
+            raise ValueError("gather_rows_i32 takes device arrays")
+        n, size = int(src.shape[0]), int(rows.shape[1]) if len(rows.shape) > 1 else 1
+        if out is None:
+            out = self.empty((n,) + tuple(rows.shape[1:]), np.int32)
+        self._ck(self.lib.pmmg_hip_gather_rows_i32(self.h, n, _p(src), size, _p(rows), _p(out)), "gather_rows_i32")
+        return out
+
+    def merged_from_groups(self, merge, xyz, met=None, fields=()):
+        """The point rows of the merged mesh from the groups' (device arrays
+        [sum np, size], groups concatenated, as groups_from_split's "owned"
+        arrays are): gathered through merge["src_pt"] with gather_rows.  Returns
+        (xyz, met or None, [fields]) of merge["np"] rows each."""
+        src = merge["src_pt"]
+        return (self.gather_rows(src, xyz), None if met is None else self.gather_rows(src, met),
+                [self.gather_rows(src, f) for f in fields])
+
     # ------------------------------------------------------------------ split over GPUs (RCCL)
     @staticmethod
     def comm_unique_id() -> bytes:

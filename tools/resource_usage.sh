@@ -2,7 +2,7 @@
 # Per-kernel VGPRs / scratch / occupancy / LDS of the HIP module, from the
 # compiler's resource-usage remarks (same flags as parmmg_amd/build.py).
 #   bash tools/resource_usage.sh [kernel-name-regex]
-# SRC=pmmg_graph.hip (or another translation unit of parmmg_amd/csrc) instead of pmmg_hip.hip
+# SRC=pmmg_graph.hip (or pmmg_merge.hip, or another translation unit of parmmg_amd/csrc) instead of pmmg_hip.hip
 set -o pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$(mktemp -d)
