@@ -65,7 +65,9 @@ def build_hip(force: bool = False) -> str:
     split = os.path.join(CSRC, "pmmg_split.hip")
     moveifc = os.path.join(CSRC, "pmmg_moveifc.hip")
     merge = os.path.join(CSRC, "pmmg_merge.hip")
-    deps = [src, snap, qual, mstats, graph, contig, split, moveifc, merge, os.path.join(INC, "parmmg_hip.h"), __file__] + [
+    gather = os.path.join(CSRC, "pmmg_gather.hip")
+    deps = [src, snap, qual, mstats, graph, contig, split, moveifc, merge, gather, os.path.join(INC, "parmmg_hip.h"),
+            __file__] + [
         os.path.join(CSRC, h) for h in ("pmmg_device.hpp", "pmmg_prep.hpp", "pmmg_vol.hpp", "pmmg_bdy.hpp",
                                         "pmmg_fallback.hpp", "pmmg_snapshot.hpp", "pmmg_quality.hpp",
                                         "pmmg_meshstats.hpp", "pmmg_graph.hpp", "pmmg_sort.hpp", "pmmg_comm.hpp",
@@ -73,7 +75,7 @@ def build_hip(force: bool = False) -> str:
                                         "pmmg_carry.hpp", "pmmg_call.hpp", "pmmg_groups.hpp", "pmmg_contig.hpp",
                                         "pmmg_contig_decide.hpp", "pmmg_tetview.hpp", "pmmg_blockscan.hpp",
                                         "pmmg_split.hpp", "pmmg_moveifc.hpp", "pmmg_moveifc_decide.hpp",
-                                        "pmmg_merge.hpp", "pmmg_merge_tables.hpp")]
+                                        "pmmg_merge.hpp", "pmmg_merge_tables.hpp", "pmmg_gather.hpp")]
     if force or _stale(out, deps):
         # max-memory-clause scheduling: the gathers of a step issued as clauses
         # (volume kernel -4.6 % at cfg4, same registers; profiles/r02e/sweep_sched_strategy.txt)
@@ -81,7 +83,7 @@ def build_hip(force: bool = False) -> str:
               "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
               # (r05: flowing off a lambda that a `return 0` made non-void is undefined: a host segfault)
               "-Werror=return-type", f"-I{INC}", "-o", out, src, snap, qual, mstats, graph, contig,
-              split, moveifc, merge])
+              split, moveifc, merge, gather])
     return out
 
 
@@ -89,8 +91,8 @@ def build_host(force: bool = False) -> str:
     src = os.path.join(CSRC, "pmmg_host.c")
     shard = os.path.join(CSRC, "pmmg_shard.c")
     medit = os.path.join(CSRC, "pmmg_medit.c")
-    deps = [src, shard, medit, os.path.join(CSRC, "pmmg_host.h"), os.path.join(CSRC, "pmmg_medit.h"),
-            os.path.join(INC, "parmmg_hip.h"), HIP_SO, __file__]
+    deps = [src, shard, medit, os.path.join(CSRC, "pmmg_host.h"), os.path.join(CSRC, "pmmg_stage.h"),
+            os.path.join(CSRC, "pmmg_medit.h"), os.path.join(INC, "parmmg_hip.h"), HIP_SO, __file__]
     if force or _stale(HOST_SO, deps):
         # -fopenmp: the halo-shard builder (pmmg_shard.c) runs its passes over
         # the group's tetra on the host threads

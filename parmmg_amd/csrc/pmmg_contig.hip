@@ -37,10 +37,10 @@
 //
 // Table: heads are the tetra with L[k] == k; block counts and a scan give
 // every head its row in ascending order.  Sizes are counted per block in an
-// LDS table and leave once per block and distinct row (a wave whose 64 tetra
-// share a row adds 64 with one lane); `exit` is a minimum over the rim, with
-// the current value read first and the atomic skipped when the candidate is
-// not lower.  No per-tetra atomic goes to a per-subgroup word.
+// LDS table (CountTable, pmmg_devutil.hpp) and leave once per block and
+// distinct row (a wave whose 64 tetra share a row adds 64 with one lane);
+// `exit` is a minimum over the rim (atomic_lower).  No per-tetra atomic goes to
+// a per-subgroup word.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -56,12 +56,9 @@ static_assert(sizeof(ContigSub) == sizeof(pmmg_hip_subgroup), "the table's rows 
 
 namespace {
 
-constexpr int kCBlock = 256;
-constexpr int kCWaves = kCBlock / 64;
-constexpr int kCMaxBlocks = 2048; // grid-stride kernels: k + stride stays below 2^30 for ne < 2^29
-constexpr int kCSlots = 1024;     // LDS size table of a block
-constexpr int kCProbe = 8;        // slots tried before a count goes to the global word directly
-constexpr int kCJumps = 16;       // parents followed per tetra and flatten pass
+constexpr int kCJumps = 16; // parents followed per tetra and flatten pass
+// the size table of a block: 1024 slots, 8 tried before a count goes to the row's word directly
+typedef CountTable<1024, 8> SizeTable;
 
 // the call's own flag bit, beside the MESH_ bits of pmmg_devutil.hpp
 enum { C_BADPART = 2 };
@@ -70,11 +67,11 @@ enum { W_FLAGS = 0, W_PASS = 1, W_VMAX = 2, W_COUNT = 4 };
 
 // Round 1 and the checks.  P[k] = -1 for an unused row, else the lowest same-colour neighbour below k, or k.
 // flags: a link out of range, a colour outside [0, ncolor), an unused row seen.
-__global__ __launch_bounds__(kCBlock) void k_contig_init(int ne, const int4 *tetv, int tstride, const int4 *adja,
+__global__ __launch_bounds__(kPBlock) void k_contig_init(int ne, const int4 *tetv, int tstride, const int4 *adja,
                                                          int astride, const int *part, int ncolor, int *P, int *flags) {
   int bad = 0;
-  const int stride = (int)gridDim.x * kCBlock;
-  for (int k = (int)blockIdx.x * kCBlock + (int)threadIdx.x; k < ne; k += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < ne; k += stride) {
     if (tetv && tetv[(size_t)k * tstride].x <= 0) {
       P[k] = -1;
       bad |= MESH_UNUSED;
@@ -102,11 +99,11 @@ __global__ __launch_bounds__(kCBlock) void k_contig_init(int ne, const int4 *tet
 
 // One hooking round on a flat forest: L[k] = P[k] = k's root.  L is only read; the hooks go to P, at roots, whose
 // P word holds the root itself until then.  *changed: a plain store of 1 by whoever hooked.
-__global__ __launch_bounds__(kCBlock) void k_contig_hook(int ne, const int4 *adja, int astride, const int *part,
+__global__ __launch_bounds__(kPBlock) void k_contig_hook(int ne, const int4 *adja, int astride, const int *part,
                                                          const int *L, int *P, int *changed) {
   bool ch = false;
-  const int stride = (int)gridDim.x * kCBlock;
-  for (int k = (int)blockIdx.x * kCBlock + (int)threadIdx.x; k < ne; k += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < ne; k += stride) {
     const int lk = L[k];
     if (lk < 0) continue;
     const int c = part ? part[k] : 0;
@@ -131,10 +128,10 @@ __global__ __launch_bounds__(kCBlock) void k_contig_hook(int ne, const int4 *adj
 // A root's own word is not written by this kernel, so a chase that met one has met the final one, and a pass in
 // which every chase did has left L[k] = P[k] = the root.  *unfinished: a plain store of 1 by a tetra whose chase
 // stopped at the bound.
-__global__ __launch_bounds__(kCBlock) void k_contig_flatten(int ne, int jumps, int *P, int *L, int *unfinished) {
+__global__ __launch_bounds__(kPBlock) void k_contig_flatten(int ne, int jumps, int *P, int *L, int *unfinished) {
   bool left = false;
-  const int stride = (int)gridDim.x * kCBlock;
-  for (int k = (int)blockIdx.x * kCBlock + (int)threadIdx.x; k < ne; k += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < ne; k += stride) {
     const int p = P[k];
     int r = p;
     if (p >= 0 && p != k) {
@@ -156,59 +153,38 @@ __global__ __launch_bounds__(kCBlock) void k_contig_flatten(int ne, int jumps, i
 }
 
 // heads (L[k] == k) of block b = tetra 256 b .. 256 b + 255
-__global__ __launch_bounds__(kCBlock) void k_contig_heads_count(int ne, const int *L, int *btot) {
-  __shared__ int wt[kCWaves];
-  const int k = (int)blockIdx.x * kCBlock + (int)threadIdx.x;
+__global__ __launch_bounds__(kPBlock) void k_contig_heads_count(int ne, const int *L, int *btot) {
+  __shared__ int wt[kPWaves];
+  const int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x;
   const int c = (k < ne && L[k] == k) ? 1 : 0;
-  const int n = block_reduce<kCWaves>(c, wt, IntSum());
+  const int n = block_reduce<kPWaves>(c, wt, IntSum());
   if (threadIdx.x == 0) btot[blockIdx.x] = n;
 }
 
 // a head's row in the table (ascending head) and the row's start values
-__global__ __launch_bounds__(kCBlock) void k_contig_heads_fill(int ne, const int *L, const int *part, const int *boff,
+__global__ __launch_bounds__(kPBlock) void k_contig_heads_fill(int ne, const int *L, const int *part, const int *boff,
                                                                int *idx, ContigSub *sub) {
-  __shared__ int wt[kCWaves];
-  const int k = (int)blockIdx.x * kCBlock + (int)threadIdx.x;
+  __shared__ int wt[kPWaves];
+  const int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x;
   const bool head = k < ne && L[k] == k;
   int n;
-  const int pos = boff[blockIdx.x] + block_prefix<kCWaves>(head ? 1 : 0, wt, &n);
+  const int pos = boff[blockIdx.x] + block_prefix<kPWaves>(head ? 1 : 0, wt, &n);
   if (head) {
     idx[k] = pos;
     sub[pos] = ContigSub{part ? part[k] : 0, k + 1, 0, INT_MAX};
   }
 }
 
-// n tetra more in row t: into the block's table, or to the row's word when kCProbe slots are taken by others
-__device__ __forceinline__ void size_add(int *s_key, int *s_cnt, ContigSub *sub, int t, int n) {
-  unsigned int h = ((unsigned int)t * 2654435761u) >> 22;
-  for (int i = 0; i < kCProbe; i++) {
-    const int old = atomicCAS(&s_key[h], -1, t);
-    if (old == -1 || old == t) {
-      atomicAdd(&s_cnt[h], n);
-      return;
-    }
-    h = (h + 1) & (kCSlots - 1);
-  }
-  atomicAdd(&sub[t].size, n);
-}
-
-__device__ __forceinline__ void exit_min(ContigSub *sub, int t, int cand) {
-  if (cand < __hip_atomic_load(&sub[t].exit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-    (void)__hip_atomic_fetch_min(&sub[t].exit, cand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Sizes and exits of the rows.  A tetra's candidate is its lowest face towards another colour, 4 (k+1) + f.
-__global__ __launch_bounds__(kCBlock) void k_contig_stats(int ne, const int4 *adja, int astride, const int *part,
+__global__ __launch_bounds__(kPBlock) void k_contig_stats(int ne, const int4 *adja, int astride, const int *part,
                                                           const int *L, const int *idx, ContigSub *sub) {
-  __shared__ int s_key[kCSlots], s_cnt[kCSlots];
-  for (int i = (int)threadIdx.x; i < kCSlots; i += kCBlock) {
-    s_key[i] = -1;
-    s_cnt[i] = 0;
-  }
+  __shared__ SizeTable sizes;
+  const auto size_of = [sub](int t) { return &sub[t].size; };
+  sizes.clear<kPBlock>();
   __syncthreads();
-  const int stride = (int)gridDim.x * kCBlock;
+  const int stride = (int)gridDim.x * kPBlock;
   const int lane = threadIdx.x & 63;
-  for (int k0 = (int)blockIdx.x * kCBlock; k0 < ne; k0 += stride) { // (block-uniform: every lane is here)
+  for (int k0 = (int)blockIdx.x * kPBlock; k0 < ne; k0 += stride) { // (block-uniform: every lane is here)
     const int k = k0 + (int)threadIdx.x;
     const int l = k < ne ? L[k] : -1;
     const int t = l >= 0 ? idx[l] : -1;
@@ -229,24 +205,23 @@ __global__ __launch_bounds__(kCBlock) void k_contig_stats(int ne, const int4 *ad
           cand = y < cand ? y : cand;
         }
         if (lane == 0) {
-          size_add(s_key, s_cnt, sub, t0, 64);
-          if (cand != INT_MAX) exit_min(sub, t0, cand);
+          sizes.add(t0, 64, size_of);
+          if (cand != INT_MAX) atomic_lower(&sub[t0].exit, cand);
         }
       }
     } else if (t >= 0) {
-      size_add(s_key, s_cnt, sub, t, 1);
-      if (cand != INT_MAX) exit_min(sub, t, cand);
+      sizes.add(t, 1, size_of);
+      if (cand != INT_MAX) atomic_lower(&sub[t].exit, cand);
     }
   }
   __syncthreads();
-  for (int i = (int)threadIdx.x; i < kCSlots; i += kCBlock)
-    if (s_key[i] >= 0) atomicAdd(&sub[s_key[i]].size, s_cnt[i]);
+  sizes.flush<kPBlock>(size_of);
 }
 
 // exit INT_MAX -> 0 (the row touches no other colour); else the colour across it
-__global__ __launch_bounds__(kCBlock) void k_contig_exits(int nsub, const int *adja, int astride, const int *part,
+__global__ __launch_bounds__(kPBlock) void k_contig_exits(int nsub, const int *adja, int astride, const int *part,
                                                           ContigSub *sub, int *exitcol) {
-  const int i = (int)blockIdx.x * kCBlock + (int)threadIdx.x;
+  const int i = (int)blockIdx.x * kPBlock + (int)threadIdx.x;
   if (i >= nsub) return;
   const int e = sub[i].exit;
   if (e == INT_MAX) {
@@ -259,10 +234,10 @@ __global__ __launch_bounds__(kCBlock) void k_contig_exits(int nsub, const int *a
 }
 
 // head[k] = the subgroup's lowest tetra (1-based), flag[k] = rank[its row]; 0 for an unused tetra
-__global__ __launch_bounds__(kCBlock) void k_contig_write(int ne, const int *L, const int *idx, const int *rank,
+__global__ __launch_bounds__(kPBlock) void k_contig_write(int ne, const int *L, const int *idx, const int *rank,
                                                           int *head, int *flag) {
-  const int stride = (int)gridDim.x * kCBlock;
-  for (int k = (int)blockIdx.x * kCBlock + (int)threadIdx.x; k < ne; k += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < ne; k += stride) {
     const int l = L[k];
     if (head) head[k] = l + 1;
     if (flag) flag[k] = l >= 0 ? rank[idx[l]] : 0;
@@ -270,10 +245,10 @@ __global__ __launch_bounds__(kCBlock) void k_contig_write(int ne, const int *L, 
 }
 
 // part[k] = target[its row] where that is a colour (>= 0)
-__global__ __launch_bounds__(kCBlock) void k_contig_apply(int ne, const int *L, const int *idx, const int *target,
+__global__ __launch_bounds__(kPBlock) void k_contig_apply(int ne, const int *L, const int *idx, const int *target,
                                                           int *part) {
-  const int stride = (int)gridDim.x * kCBlock;
-  for (int k = (int)blockIdx.x * kCBlock + (int)threadIdx.x; k < ne; k += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < ne; k += stride) {
     const int l = L[k];
     if (l < 0) continue;
     const int t = target[idx[l]];
@@ -282,15 +257,15 @@ __global__ __launch_bounds__(kCBlock) void k_contig_apply(int ne, const int *L, 
 }
 
 // the largest vertex id of the tetra (np of a call that builds its adjacency): one atomic per block
-__global__ __launch_bounds__(kCBlock) void k_contig_vmax(int ne, const int4 *tetv, int *vmax) {
-  __shared__ int wt[kCWaves];
+__global__ __launch_bounds__(kPBlock) void k_contig_vmax(int ne, const int4 *tetv, int *vmax) {
+  __shared__ int wt[kPWaves];
   int m = 0;
-  const int stride = (int)gridDim.x * kCBlock;
-  for (int k = (int)blockIdx.x * kCBlock + (int)threadIdx.x; k < ne; k += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < ne; k += stride) {
     const int4 v = tetv[k];
     m = max(max(m, max(v.x, v.y)), max(v.z, v.w));
   }
-  m = block_reduce<kCWaves>(m, wt, IntMax());
+  m = block_reduce<kPWaves>(m, wt, IntMax());
   if (threadIdx.x == 0) atomicMax(vmax, m);
 }
 
@@ -298,11 +273,6 @@ int ceil_log2(int n) {
   int b = 0;
   while (b < 31 && (1LL << b) < n) b++;
   return b;
-}
-
-int grid_for(int ne) {
-  const int b = (ne + kCBlock - 1) / kCBlock;
-  return b < 1 ? 1 : (b > kCMaxBlocks ? kCMaxBlocks : b);
 }
 
 // the link rows of a call that came without any, built into the cache; np = the largest vertex id
@@ -314,8 +284,8 @@ int ensure_adja(hipStream_t s, TetView *m, ContigCache *c, SnapCache *snap, char
     return 0;
   }
   DEVCK(hipMemsetAsync(words, 0, W_COUNT * sizeof(int), s));
-  hipLaunchKernelGGL(k_contig_vmax, dim3(grid_for(m->ne)), dim3(kCBlock), 0, s, m->ne,
-                     reinterpret_cast<const int4 *>(m->tetv), words + W_VMAX);
+  hipLaunchKernelGGL(k_contig_vmax, dim3(grid_for(m->ne)), dim3(kPBlock), 0, s, m->ne, rows_of(*m).tetv,
+                     words + W_VMAX);
   DEVCK(hipGetLastError());
   int np = 0;
   if (!read_word(s, words + W_VMAX, &np, msg, msglen)) return 0;
@@ -338,10 +308,10 @@ int label(hipStream_t s, const TetView &m, const int *part, int ncolor, bool fre
     snprintf(msg, msglen, "contiguity: out of device memory (labels of %d tetra)", ne);
     return 0;
   }
-  const int4 *tv = reinterpret_cast<const int4 *>(m.tetv), *av = reinterpret_cast<const int4 *>(m.adja);
+  const int4 *tv = rows_of(m).tetv, *av = rows_of(m).adja;
   if (fresh) {
     DEVCK(hipMemsetAsync(words, 0, W_COUNT * sizeof(int), s));
-    hipLaunchKernelGGL(k_contig_init, dim3(grid), dim3(kCBlock), 0, s, ne, tv, m.tstride, av, m.astride, part, ncolor,
+    hipLaunchKernelGGL(k_contig_init, dim3(grid), dim3(kPBlock), 0, s, ne, tv, m.tstride, av, m.astride, part, ncolor,
                        P, words + W_FLAGS);
     DEVCK(hipGetLastError());
     int f = 0;
@@ -354,7 +324,7 @@ int label(hipStream_t s, const TetView &m, const int *part, int ncolor, bool fre
       snprintf(msg, msglen, "contiguity: a used tetra has a part value outside [0, %d) (nothing written)", ncolor);
       return 0;
     }
-    if (!check_links<kCBlock>(s, "contiguity", " (nothing written)", m, words + W_FLAGS, &f, msg, msglen)) return 0;
+    if (!check_links<kPBlock>(s, "contiguity", " (nothing written)", m, words + W_FLAGS, &f, msg, msglen)) return 0;
   }
   const int cap = 2 * ceil_log2(ne > 2 ? ne : 2) + 1; // of the hooking rounds: the bound of the file's header
   const int pass_cap = ceil_log2(ne) + 2;             // of a round's flatten passes (17-fold each: ceil(log17 ne) + 1)
@@ -367,7 +337,7 @@ int label(hipStream_t s, const TetView &m, const int *part, int ncolor, bool fre
         return 0;
       }
       DEVCK(hipMemsetAsync(words + W_PASS, 0, sizeof(int), s));
-      hipLaunchKernelGGL(k_contig_flatten, dim3(grid), dim3(kCBlock), 0, s, ne, kCJumps, P, L, words + W_PASS);
+      hipLaunchKernelGGL(k_contig_flatten, dim3(grid), dim3(kPBlock), 0, s, ne, kCJumps, P, L, words + W_PASS);
       DEVCK(hipGetLastError());
       c->passes++;
       int left = 0;
@@ -379,7 +349,7 @@ int label(hipStream_t s, const TetView &m, const int *part, int ncolor, bool fre
       return 0;
     }
     DEVCK(hipMemsetAsync(words + W_PASS, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_contig_hook, dim3(grid), dim3(kCBlock), 0, s, ne, av, m.astride, part, L, P, words + W_PASS);
+    hipLaunchKernelGGL(k_contig_hook, dim3(grid), dim3(kPBlock), 0, s, ne, av, m.astride, part, L, P, words + W_PASS);
     DEVCK(hipGetLastError());
     nround++;
     int changed = 0;
@@ -394,7 +364,7 @@ int label(hipStream_t s, const TetView &m, const int *part, int ncolor, bool fre
 // the table of the labelled forest, on the device (cache->sub, ->exitcol, ->idx) and on the host
 int table(hipStream_t s, const TetView &m, const int *part, ContigCache *c, std::vector<ContigSub> *T,
           std::vector<int> *exitcol, char *msg, size_t msglen) {
-  const int ne = m.ne, nblk = (ne + kCBlock - 1) / kCBlock;
+  const int ne = m.ne, nblk = (ne + kPBlock - 1) / kPBlock;
   const int *L = c->label.as<int>();
   char oom[96];
   snprintf(oom, sizeof(oom), "contiguity: out of device memory (table index of %d tetra)", ne);
@@ -402,7 +372,7 @@ int table(hipStream_t s, const TetView &m, const int *part, ContigCache *c, std:
   if (!idx) return refuse(msg, msglen, oom);
   if (!reserve(c->heads, nblk, s, oom, msg, msglen)) return 0;
   const int *boff = c->heads.boff.as<int>();
-  hipLaunchKernelGGL(k_contig_heads_count, dim3(nblk), dim3(kCBlock), 0, s, ne, L, c->heads.btot.as<int>());
+  hipLaunchKernelGGL(k_contig_heads_count, dim3(nblk), dim3(kPBlock), 0, s, ne, L, c->heads.btot.as<int>());
   DEVCK(hipGetLastError());
   int nsub = 0;
   if (!offsets(c->heads, s, nblk, &nsub, msg, msglen)) return 0;
@@ -415,10 +385,10 @@ int table(hipStream_t s, const TetView &m, const int *part, ContigCache *c, std:
     snprintf(msg, msglen, "contiguity: out of device memory (table of %d subgroups)", nsub);
     return 0;
   }
-  const int4 *av = reinterpret_cast<const int4 *>(m.adja);
-  hipLaunchKernelGGL(k_contig_heads_fill, dim3(nblk), dim3(kCBlock), 0, s, ne, L, part, boff, idx, sub);
-  hipLaunchKernelGGL(k_contig_stats, dim3(grid_for(ne)), dim3(kCBlock), 0, s, ne, av, m.astride, part, L, idx, sub);
-  hipLaunchKernelGGL(k_contig_exits, dim3((nsub + kCBlock - 1) / kCBlock), dim3(kCBlock), 0, s, nsub, m.adja,
+  const int4 *av = rows_of(m).adja;
+  hipLaunchKernelGGL(k_contig_heads_fill, dim3(nblk), dim3(kPBlock), 0, s, ne, L, part, boff, idx, sub);
+  hipLaunchKernelGGL(k_contig_stats, dim3(grid_for(ne)), dim3(kPBlock), 0, s, ne, av, m.astride, part, L, idx, sub);
+  hipLaunchKernelGGL(k_contig_exits, dim3((nsub + kPBlock - 1) / kPBlock), dim3(kPBlock), 0, s, nsub, m.adja,
                      m.astride, part, sub, ec);
   DEVCK(hipGetLastError());
   DEVCK(hipMemcpyAsync(T->data(), sub, sizeof(ContigSub) * (size_t)nsub, hipMemcpyDeviceToHost, s));
@@ -455,7 +425,7 @@ int pmmg_contig_subgroups(hipStream_t s, TetView m, const int *part, int ncolor,
     for (size_t i = 0; i < T.size(); i++) rank[i] = ++seen[(size_t)T[i].color];
     int *d_rank = cache->rank.as<int>();
     if (!T.empty()) DEVCK(hipMemcpyAsync(d_rank, rank.data(), sizeof(int) * rank.size(), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_contig_write, dim3(grid_for(m.ne)), dim3(kCBlock), 0, s, m.ne, cache->label.as<int>(),
+    hipLaunchKernelGGL(k_contig_write, dim3(grid_for(m.ne)), dim3(kPBlock), 0, s, m.ne, cache->label.as<int>(),
                        cache->idx.as<int>(), d_rank, head, flag);
     DEVCK(hipGetLastError());
     DEVCK(hipStreamSynchronize(s)); // (rank is read by the copy until here)
@@ -510,7 +480,7 @@ int pmmg_contig_fix(hipStream_t s, TetView m, int *part, int ncolor, int64_t *nm
     stale = true;
     int *d_target = cache->rank.as<int>();
     DEVCK(hipMemcpyAsync(d_target, target.data(), sizeof(int) * target.size(), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_contig_apply, dim3(grid_for(m.ne)), dim3(kCBlock), 0, s, m.ne, cache->label.as<int>(),
+    hipLaunchKernelGGL(k_contig_apply, dim3(grid_for(m.ne)), dim3(kPBlock), 0, s, m.ne, cache->label.as<int>(),
                        cache->idx.as<int>(), d_target, part);
     DEVCK(hipGetLastError());
     DEVCK(hipStreamSynchronize(s));

@@ -1,9 +1,11 @@
 // pmmg_devutil.hpp — what the mesh services (pmmg_snapshot.hip, pmmg_meshstats.hip, pmmg_graph.hip,
-// pmmg_contig.hip) share.  Device side (beside pmmg_blockscan.hpp's prefix and reduction over a block):
-// the range check of a link, the flag bits of a pass over the links, the kernel that looks for a link to
-// an unused row.  Host side: the error macro of a function that reports through (msg, msglen) and returns
-// 0, a word read back, the exclusive scan of an int array, the two operations of a BlockScan, and the two
-// steps the graph and the contiguity calls share.
+// pmmg_contig.hip, pmmg_split.hip, pmmg_moveifc.hip, pmmg_merge.hip, pmmg_gather.hip) share.  Device side
+// (beside pmmg_blockscan.hpp's prefix and reduction over a block): the block and grid of the group services,
+// the tetra rows as a kernel reads them, the range check of a link, the flag bits of a pass over the links,
+// the kernel that looks for a link to an unused row, the guarded atomic minimum, the count table of a block
+// in LDS.  Host side: the error macro of a function that reports through (msg, msglen) and returns 0, a word
+// read back, the exclusive scan of an int array, the two operations of a BlockScan, and the two steps the
+// graph and the contiguity calls share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -16,8 +18,78 @@
 
 // ---------------------------------------------------------------- device side
 
+// The block of the kernels that serve a partition (kP: contiguity, split, interface displacement, merge,
+// gather) and the grid of a grid-stride kernel over n items: an index below 2^29 plus the stride, at most
+// 2048 * 256 = 2^19, stays below 2^30, so the loops count in an int.
+constexpr int kPBlock = 256;
+constexpr int kPWaves = kPBlock / 64;
+constexpr int kPMaxBlocks = 2048;
+
+static inline int grid_for(long long n) {
+  const long long b = (n + kPBlock - 1) / kPBlock;
+  return b < 1 ? 1 : (b > kPMaxBlocks ? kPMaxBlocks : (int)b);
+}
+
+// The rows of a TetView as a kernel reads them: one 16-byte load a row.
+struct TetRows {
+  int ne;
+  const int4 *tetv;
+  int tstride;
+  const int4 *adja;
+  int astride;
+};
+static inline TetRows rows_of(const TetView &v) {
+  return TetRows{v.ne, reinterpret_cast<const int4 *>(v.tetv), v.tstride, reinterpret_cast<const int4 *>(v.adja),
+                 v.astride};
+}
+
 // a link 4 k' + i' of a mesh of ne tetra lies in [4, 4 ne + 3]
 __device__ __forceinline__ bool link_ok(int a, int ne) { return (unsigned int)(a - 4) <= 4u * (unsigned int)ne - 1u; }
+
+// *p = min(*p, key): agent scope, relaxed, nothing returned, and no atomic at all when a plain load already
+// shows a value that is not above key (words that many threads lower settle early, and most callers then
+// only read).  What the word holds afterwards does not depend on the interleaving.
+template <class T>
+__device__ __forceinline__ void atomic_lower(T *p, T key) {
+  if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+    (void)__hip_atomic_fetch_min(p, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The counts of a block per key (a key >= 0: a table row, a colour), in LDS: a __shared__ object, cleared by the
+// whole block (BLOCK threads) with a barrier after it, added to by any thread, and flushed by the whole block
+// after a barrier, one atomicAdd per key the block met.  word(key) is the key's count in global memory: a key
+// that finds PROBE slots taken by others adds there directly.
+template <int SLOTS, int PROBE>
+struct CountTable {
+  static_assert(SLOTS == 1 << 10, "the hash keeps 10 bits");
+  int key[SLOTS], cnt[SLOTS];
+
+  template <int BLOCK>
+  __device__ __forceinline__ void clear() {
+    for (int i = (int)threadIdx.x; i < SLOTS; i += BLOCK) {
+      key[i] = -1;
+      cnt[i] = 0;
+    }
+  }
+  template <class Word>
+  __device__ __forceinline__ void add(int k, int n, Word word) {
+    unsigned int h = ((unsigned int)k * 2654435761u) >> 22;
+    for (int i = 0; i < PROBE; i++) {
+      const int old = atomicCAS(&key[h], -1, k);
+      if (old == -1 || old == k) {
+        atomicAdd(&cnt[h], n);
+        return;
+      }
+      h = (h + 1) & (SLOTS - 1);
+    }
+    atomicAdd(word(k), n);
+  }
+  template <int BLOCK, class Word>
+  __device__ __forceinline__ void flush(Word word) {
+    for (int i = (int)threadIdx.x; i < SLOTS; i += BLOCK)
+      if (key[i] >= 0) atomicAdd(word(key[i]), cnt[i]);
+  }
+};
 
 // Flag bits of a pass over the links of a mesh.  Bit 2 is the pass's own (a vertex id, a colour).
 enum { MESH_BADLINK = 1, MESH_UNUSED = 4, MESH_TOUNUSED = 8 };
@@ -115,9 +187,9 @@ int check_links(hipStream_t s, const char *who, const char *tail, const TetView 
                 char *msg, size_t msglen) {
   if (!(*h_flags & MESH_UNUSED)) return 1;
   const int nblk = (m.ne + BLOCK - 1) / BLOCK;
-  hipLaunchKernelGGL(k_links_to_unused<BLOCK>, dim3(nblk < 2048 ? nblk : 2048), dim3(BLOCK), 0, s, m.ne,
-                     reinterpret_cast<const int4 *>(m.tetv), m.tstride, reinterpret_cast<const int4 *>(m.adja),
-                     m.astride, flags);
+  const TetRows r = rows_of(m);
+  hipLaunchKernelGGL(k_links_to_unused<BLOCK>, dim3(nblk < kPMaxBlocks ? nblk : kPMaxBlocks), dim3(BLOCK), 0, s,
+                     m.ne, r.tetv, r.tstride, r.adja, r.astride, flags);
   DEVCK(hipGetLastError());
   if (!read_word(s, flags, h_flags, msg, msglen)) return 0;
   if (*h_flags & MESH_TOUNUSED) {

@@ -32,6 +32,7 @@
 #include "pmmg_call.hpp"   // one call on device pointers: Call, its stages, run_device, collect_stats
 #include "pmmg_groups.hpp" // the groups call's lanes
 #include "pmmg_comm.hpp"   // the RCCL loader and the all-gather
+#include "pmmg_gather.hpp"
 #include "pmmg_quality.hpp"
 
 extern "C" {
@@ -861,19 +862,25 @@ int pmmg_hip_split_groups(pmmg_hip_ctx *c, int np, int ne, const int *tetv, cons
   return pmmg_split_groups(c->stream, a, &c->split_cache, c->err, sizeof(c->err));
 }
 
-int pmmg_hip_gather_rows(pmmg_hip_ctx *c, int64_t n, const int *src, int size, const double *in, double *out) {
+// the two gathers (pmmg_gather.hip): rows of `size` elements of `elem` bytes; `unaligned` is the call's own text
+static int gather_rows(pmmg_hip_ctx *c, const char *who, const char *unaligned, int64_t n, const int *src, int size,
+                       int elem, const void *in, void *out) {
   if (!enter(c)) return 0;
   if (n < 0 || size < 1 || (n > 0 && (!src || !in || !out))) {
-    set_err(c, "gather_rows: invalid arguments (n=%lld size=%d)", (long long)n, size);
+    set_err(c, "%s: invalid arguments (n=%lld size=%d)", who, (long long)n, size);
     return 0;
   }
-  if (!aligned<4>(src) || !aligned<8>(in) || !aligned<8>(out)) {
-    set_err(c, "gather_rows: src must be 4-byte, in / out 8-byte aligned");
+  if (!aligned<4>(src) || ((uintptr_t)in | (uintptr_t)out) % (uintptr_t)elem) {
+    set_err(c, "%s: %s", who, unaligned);
     return 0;
   }
-  if (!pmmg_split_gather(c->stream, n, src, size, in, out, c->err, sizeof(c->err))) return 0;
+  if (!pmmg_gather_rows(c->stream, n, src, (int64_t)size * elem, elem, in, out, c->err, sizeof(c->err))) return 0;
   HIPCK(c, hipStreamSynchronize(c->stream));
   return 1;
+}
+
+int pmmg_hip_gather_rows(pmmg_hip_ctx *c, int64_t n, const int *src, int size, const double *in, double *out) {
+  return gather_rows(c, "gather_rows", "src must be 4-byte, in / out 8-byte aligned", n, src, size, 8, in, out);
 }
 
 int pmmg_hip_split_rounds(pmmg_hip_ctx *c) { return c ? c->split_cache.rounds : -1; }
@@ -925,18 +932,7 @@ int pmmg_hip_merge_groups(pmmg_hip_ctx *c, int ngrp, const pmmg_hip_split_count 
 }
 
 int pmmg_hip_gather_rows_i32(pmmg_hip_ctx *c, int64_t n, const int *src, int size, const int *in, int *out) {
-  if (!enter(c)) return 0;
-  if (n < 0 || size < 1 || (n > 0 && (!src || !in || !out))) {
-    set_err(c, "gather_rows_i32: invalid arguments (n=%lld size=%d)", (long long)n, size);
-    return 0;
-  }
-  if (!aligned<4>(src) || !aligned<4>(in) || !aligned<4>(out)) {
-    set_err(c, "gather_rows_i32: src, in and out must be 4-byte aligned");
-    return 0;
-  }
-  if (!pmmg_merge_gather_i32(c->stream, n, src, size, in, out, c->err, sizeof(c->err))) return 0;
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  return 1;
+  return gather_rows(c, "gather_rows_i32", "src, in and out must be 4-byte aligned", n, src, size, 4, in, out);
 }
 
 // ---- interface displacement (pmmg_moveifc.hip)

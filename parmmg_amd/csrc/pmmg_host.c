@@ -5,6 +5,7 @@
  */
 #define _GNU_SOURCE
 #include "pmmg_host.h"
+#include "pmmg_stage.h"
 #include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -150,6 +151,12 @@ int pmmg_set_constant_metric(pmmg_new_group *g) {
   return 1;
 }
 
+/* 1 with a context; else 0, after the message of an entry point (`what`) that has nothing to run on */
+static int have_ctx(const pmmg_hip_ctx *ctx, const char *what) {
+  if (!ctx) fprintf(stderr, "[parmmg_host] no HIP context: %s has no CPU fallback\n", what);
+  return ctx != NULL;
+}
+
 static void stats_add(pmmg_hip_stats *a, const pmmg_hip_stats *b) {
   a->nvol += b->nvol; a->nbdy += b->nbdy;
   a->nvol_walk += b->nvol_walk; a->nvol_exhaust += b->nvol_exhaust; a->nvol_closest += b->nvol_closest;
@@ -171,10 +178,7 @@ static void stats_add(pmmg_hip_stats *a, const pmmg_hip_stats *b) {
 static int interp_groups(pmmg_hip_ctx *ctx, int ngrp, const pmmg_old_group *old, pmmg_new_group *grp, int input_met,
                          int keep, int carried, const int *const *src, const int *const *pmap,
                          pmmg_hip_stats *stats) {
-  if (!ctx) {
-    fprintf(stderr, "[parmmg_host] no HIP context: the transfer step has no CPU fallback\n");
-    return 0;
-  }
+  if (!have_ctx(ctx, "the transfer step")) return 0;
   if (stats) memset(stats, 0, sizeof(*stats));
   int ier = 1;
   for (int ig = 0; ig < ngrp; ig++) {
@@ -256,10 +260,7 @@ void pmmg_host_free(void *p) { free(p); }
 int pmmg_graph_mesh_elts2metis(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne, const int *tetv, const int *adja,
                                int met_size, const double *met, int want_wgt, int **xadj, int **adjncy, int **adjwgt,
                                int64_t *nadjncy) {
-  if (!ctx) {
-    fprintf(stderr, "[parmmg_host] no HIP context: the element graph has no CPU fallback\n");
-    return 0;
-  }
+  if (!have_ctx(ctx, "the element graph")) return 0;
   if (!xadj || !adjncy || !adjwgt || !nadjncy || np < 0 || ne < 0 || (ne > 0 && !tetv) ||
       (want_wgt && ne > 0 && !xyz) || ne >= (1 << 29))
     return 0;
@@ -268,31 +269,17 @@ int pmmg_graph_mesh_elts2metis(pmmg_hip_ctx *ctx, int np, const double *xyz, int
   if (!met) met_size = 0; /* no metric: PMMG_computeWgt gives PMMG_WGTVAL_HUGEINT */
   const int wgt = want_wgt != 0;
   const int64_t cap = 4 * (int64_t)ne; /* device arrays for every face; the host ones are sized from the count */
-  void *d_xyz = NULL, *d_tetv = NULL, *d_adja = NULL, *d_met = NULL, *d_xadj = NULL, *d_adj = NULL, *d_wgt = NULL;
+  const int64_t i4 = (int64_t)sizeof(int), d8 = (int64_t)sizeof(double);
   int *h_xadj = NULL, *h_adj = NULL, *h_wgt = NULL;
-  int ok = 1;
-#define UP(dst, src, bytes)                                                                    \
-  do {                                                                                         \
-    if (ok && (bytes) > 0) {                                                                   \
-      (dst) = pmmg_hip_malloc(ctx, (int64_t)(bytes));                                          \
-      ok = (dst) != NULL && pmmg_hip_memcpy_h2d(ctx, (dst), (src), (int64_t)(bytes));          \
-    }                                                                                          \
-  } while (0)
-  UP(d_tetv, tetv, sizeof(int) * 4 * (size_t)ne);
-  if (adja) UP(d_adja, adja, sizeof(int) * 4 * (size_t)ne);
-  if (wgt) {
-    UP(d_xyz, xyz, sizeof(double) * 3 * (size_t)np);
-    if (met_size) UP(d_met, met, sizeof(double) * (size_t)met_size * (size_t)np);
-  }
-#undef UP
-  if (ok) ok = (d_xadj = pmmg_hip_malloc(ctx, (int64_t)sizeof(int) * ((int64_t)ne + 1))) != NULL;
-  if (ok) ok = (d_adj = pmmg_hip_malloc(ctx, (int64_t)sizeof(int) * cap)) != NULL;
-  if (ok && wgt) ok = (d_wgt = pmmg_hip_malloc(ctx, (int64_t)sizeof(int) * cap)) != NULL;
+  pmmg_stage st = pmmg_stage_begin(ctx);
+  const int *d_tetv = pmmg_stage_up(&st, tetv, i4 * 4 * ne), *d_adja = pmmg_stage_up(&st, adja, i4 * 4 * ne);
+  const double *d_xyz = wgt ? pmmg_stage_up(&st, xyz, d8 * 3 * np) : NULL;
+  const double *d_met = wgt ? pmmg_stage_up(&st, met, d8 * met_size * np) : NULL;
+  int *d_xadj = pmmg_stage_room(&st, i4 * ((int64_t)ne + 1)), *d_adj = pmmg_stage_room(&st, i4 * cap);
+  int *d_wgt = wgt ? pmmg_stage_room(&st, i4 * cap) : NULL;
   int64_t n = 0;
-  if (ok)
-    ok = pmmg_hip_metis_graph(ctx, np, (const double *)d_xyz, ne, (const int *)d_tetv, (const int *)d_adja, NULL,
-                              met_size, (const double *)d_met, (int)cap, &n, (int *)d_xadj, (int *)d_adj,
-                              (int *)d_wgt);
+  int ok = st.ok && pmmg_hip_metis_graph(ctx, np, d_xyz, ne, d_tetv, d_adja, NULL, met_size, d_met, (int)cap, &n,
+                                         d_xadj, d_adj, d_wgt);
   if (ok) {
     /* (the reference allocates one entry more than the count, src/metis_pmmg.c:783: never empty) */
     h_xadj = (int *)malloc(sizeof(int) * ((size_t)ne + 1));
@@ -303,9 +290,7 @@ int pmmg_graph_mesh_elts2metis(pmmg_hip_ctx *ctx, int np, const double *xyz, int
          pmmg_hip_memcpy_d2h(ctx, h_adj, d_adj, (int64_t)sizeof(int) * n) &&
          (!wgt || pmmg_hip_memcpy_d2h(ctx, h_wgt, d_wgt, (int64_t)sizeof(int) * n));
   }
-  void *dev[] = {d_xyz, d_tetv, d_adja, d_met, d_xadj, d_adj, d_wgt};
-  for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); i++)
-    if (dev[i]) pmmg_hip_free(ctx, dev[i]);
+  pmmg_stage_end(&st);
   if (!ok) {
     free(h_xadj);
     free(h_adj);
@@ -321,34 +306,16 @@ int pmmg_graph_mesh_elts2metis(pmmg_hip_ctx *ctx, int np, const double *xyz, int
 
 /* ---------------------------------------------------------------- contiguity of a partition */
 
-/* the host arrays that are given (each may be NULL), on the device: d[0] tetv, d[1] adja, d[2] part */
-static int contig_up(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *adja, const int *part, void *d[3]) {
-  const void *src[3] = {tetv, adja, part};
-  const int64_t bytes[3] = {(int64_t)sizeof(int) * 4 * ne, (int64_t)sizeof(int) * 4 * ne, (int64_t)sizeof(int) * ne};
-  d[0] = d[1] = d[2] = NULL;
-  for (int i = 0; i < 3; i++) {
-    if (!src[i] || ne == 0) continue;
-    d[i] = pmmg_hip_malloc(ctx, bytes[i]);
-    if (!d[i] || !pmmg_hip_memcpy_h2d(ctx, d[i], src[i], bytes[i])) return 0;
-  }
-  return 1;
-}
-
-static void contig_free(pmmg_hip_ctx *ctx, void *d[3]) {
-  for (int i = 0; i < 3; i++)
-    if (d[i]) pmmg_hip_free(ctx, d[i]);
-}
-
 int pmmg_check_part_contiguity(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *adja, const int *part, int ncolor,
                                int *ncomp) {
-  if (!ctx) {
-    fprintf(stderr, "[parmmg_host] no HIP context: the contiguity check has no CPU fallback\n");
-    return -1;
-  }
+  if (!have_ctx(ctx, "the contiguity check")) return -1;
   if (ne < 0 || ncolor < 1 || !ncomp || (ne > 0 && !tetv && !adja)) return -1;
-  void *d[3];
+  const int64_t i4 = (int64_t)sizeof(int);
+  pmmg_stage st = pmmg_stage_begin(ctx);
+  const int *d_tetv = pmmg_stage_up(&st, tetv, i4 * 4 * ne), *d_adja = pmmg_stage_up(&st, adja, i4 * 4 * ne);
+  const int *d_part = pmmg_stage_up(&st, part, i4 * ne);
   int64_t nsub = 0;
-  int ok = contig_up(ctx, ne, tetv, adja, part, d);
+  int ok = st.ok;
   /* the table itself is not wanted, but a call without room for it returns 0: give it room, once more when the
    * first guess was too small (the call then left *nsub, and only that refusal leaves it above cap) */
   int64_t cap = ne < 4096 ? ne : 4096;
@@ -360,33 +327,30 @@ int pmmg_check_part_contiguity(pmmg_hip_ctx *ctx, int ne, const int *tetv, const
       break;
     }
     nsub = 0;
-    ok = pmmg_hip_part_subgroups(ctx, ne, (const int *)d[0], (const int *)d[1], NULL, (const int *)d[2], ncolor, NULL,
-                                 NULL, ncomp, (int)cap, sub, &nsub, NULL);
+    ok = pmmg_hip_part_subgroups(ctx, ne, d_tetv, d_adja, NULL, d_part, ncolor, NULL, NULL, ncomp, (int)cap, sub, &nsub,
+                                 NULL);
     free(sub);
     if (ok || turn == 1 || nsub <= cap) break;
     cap = nsub;
     ok = 1;
   }
-  contig_free(ctx, d);
+  pmmg_stage_end(&st);
   return ok ? ncomp[ncolor - 1] : -1;
 }
 
 int pmmg_fix_contiguity_split(pmmg_hip_ctx *ctx, int ne, const int *tetv, const int *adja, int ngrp, int *part) {
-  if (!ctx) {
-    fprintf(stderr, "[parmmg_host] no HIP context: the contiguity fix has no CPU fallback\n");
-    return 0;
-  }
+  if (!have_ctx(ctx, "the contiguity fix")) return 0;
   if (ne < 0 || ngrp < 1 || (ne > 0 && (!part || (!tetv && !adja)))) return 0;
   if (ne == 0) return 1;
-  void *d[3];
+  const int64_t i4 = (int64_t)sizeof(int);
   int64_t nmoved = 0;
   int nmerged = 0, nstuck = 0;
-  int ok = contig_up(ctx, ne, tetv, adja, part, d);
-  if (ok)
-    ok = pmmg_hip_fix_contiguity(ctx, ne, (const int *)d[0], (const int *)d[1], NULL, (int *)d[2], ngrp, &nmoved,
-                                 &nmerged, &nstuck);
-  if (ok && nmerged) ok = pmmg_hip_memcpy_d2h(ctx, part, d[2], (int64_t)sizeof(int) * ne);
-  contig_free(ctx, d);
+  pmmg_stage st = pmmg_stage_begin(ctx);
+  const int *d_tetv = pmmg_stage_up(&st, tetv, i4 * 4 * ne), *d_adja = pmmg_stage_up(&st, adja, i4 * 4 * ne);
+  int *d_part = pmmg_stage_up(&st, part, i4 * ne);
+  int ok = st.ok && pmmg_hip_fix_contiguity(ctx, ne, d_tetv, d_adja, NULL, d_part, ngrp, &nmoved, &nmerged, &nstuck);
+  if (ok && nmerged) ok = pmmg_hip_memcpy_d2h(ctx, part, d_part, i4 * ne);
+  pmmg_stage_end(&st);
   return ok;
 }
 
@@ -396,10 +360,7 @@ int pmmg_fix_contiguity_split(pmmg_hip_ctx *ctx, int ne, const int *tetv, const 
 int pmmg_part_move_interfaces(pmmg_hip_ctx *ctx, int np, int ne, const int *tetv, const int *adja, const int *mark,
                               int ncolor, const int *weight, const int *nelem_local, int nlayers, int *part_out,
                               int *layers_done, int *blocked) {
-  if (!ctx) {
-    fprintf(stderr, "[parmmg_host] no HIP context: the interface displacement has no CPU fallback\n");
-    return 0;
-  }
+  if (!have_ctx(ctx, "the interface displacement")) return 0;
   if (np < 0 || ne < 0 || ncolor < 1 || nlayers < 0 || !weight || !nelem_local ||
       (ne > 0 && (!tetv || !mark || !part_out)))
     return 0;
@@ -408,7 +369,8 @@ int pmmg_part_move_interfaces(pmmg_hip_ctx *ctx, int np, int ne, const int *tetv
   if (blocked) *blocked = 0;
   if (ne == 0) return 1;
   int *nelem = (int *)malloc(sizeof(int) * (size_t)ncolor * 2), *moved = (int *)malloc(sizeof(int) * (size_t)(nlayers + 1));
-  void *d[3] = {NULL, NULL, NULL}, *color = NULL, *front = NULL;
+  const int64_t i4 = (int64_t)sizeof(int);
+  pmmg_stage st = pmmg_stage_begin(ctx);
   int ok = nelem && moved;
   if (ok) {
     int *nemin = nelem + ncolor;
@@ -417,28 +379,23 @@ int pmmg_part_move_interfaces(pmmg_hip_ctx *ctx, int np, int ne, const int *tetv
       const int half = nelem[g] / 2 + 1;
       nemin[g] = nelem[g] < 0 ? 0 : (half < 6 ? half : 6); /* MG_MIN(PMMG_REDISTR_NELEM_MIN, negrp/2+1) */
     }
-    ok = contig_up(ctx, ne, tetv, adja, mark, d);
-    color = ok ? pmmg_hip_malloc(ctx, (int64_t)sizeof(int) * np) : NULL;
-    front = color ? pmmg_hip_malloc(ctx, np) : NULL;
-    ok = ok && color && front;
-    if (ok) ok = pmmg_hip_ifc_seed(ctx, np, ne, (const int *)d[0], NULL, (const int *)d[2], ncolor, weight, (int *)color,
-                                   (unsigned char *)front);
+    const int *d_tetv = pmmg_stage_up(&st, tetv, i4 * 4 * ne), *d_adja = pmmg_stage_up(&st, adja, i4 * 4 * ne);
+    int *d_mark = pmmg_stage_up(&st, mark, i4 * ne), *color = pmmg_stage_room(&st, i4 * np);
+    unsigned char *front = pmmg_stage_room(&st, np);
+    ok = st.ok && pmmg_hip_ifc_seed(ctx, np, ne, d_tetv, NULL, d_mark, ncolor, weight, color, front);
     if (ok)
-      ok = pmmg_hip_ifc_layers(ctx, np, ne, (const int *)d[0], NULL, (int *)d[2], ncolor, weight, nelem, nemin,
-                               (int *)color, (unsigned char *)front, 0, NULL, NULL, nlayers, &done, &blk, moved);
+      ok = pmmg_hip_ifc_layers(ctx, np, ne, d_tetv, NULL, d_mark, ncolor, weight, nelem, nemin, color, front, 0, NULL,
+                               NULL, nlayers, &done, &blk, moved);
     if (ok && !blk) {
       int64_t nmoved = 0;
       int nmerged = 0, nstuck = 0;
-      ok = pmmg_hip_fix_contiguity(ctx, ne, (const int *)d[0], (const int *)d[1], NULL, (int *)d[2], ncolor, &nmoved,
-                                   &nmerged, &nstuck);
+      ok = pmmg_hip_fix_contiguity(ctx, ne, d_tetv, d_adja, NULL, d_mark, ncolor, &nmoved, &nmerged, &nstuck);
     }
-    if (ok) ok = pmmg_hip_memcpy_d2h(ctx, part_out, d[2], (int64_t)sizeof(int) * ne);
+    if (ok) ok = pmmg_hip_memcpy_d2h(ctx, part_out, d_mark, i4 * ne);
   }
   if (ok && layers_done) *layers_done = done;
   if (ok && blocked) *blocked = blk;
-  contig_free(ctx, d);
-  if (color) pmmg_hip_free(ctx, color);
-  if (front) pmmg_hip_free(ctx, front);
+  pmmg_stage_end(&st);
   free(nelem);
   free(moved);
   return ok;
@@ -458,24 +415,11 @@ void pmmg_split_result_free(pmmg_split_result *r) {
   memset(r, 0, sizeof(*r));
 }
 
-/* n bytes of the device block d in a new host block (one byte when n == 0, so that NULL means failure) */
-static void *split_down(pmmg_hip_ctx *ctx, const void *d, int64_t n) {
-  void *h = malloc(n > 0 ? (size_t)n : 1);
-  if (h && n > 0 && !pmmg_hip_memcpy_d2h(ctx, h, d, n)) {
-    free(h);
-    h = NULL;
-  }
-  return h;
-}
-
 int pmmg_split_grps(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne, const int *tetv, const int *adja,
                     const int *part, int ngrp, int met_size, const double *met, int nfield, const int *field_size,
                     const double *const *fields, const int *node_pos, const int *face_old, int nnode0, int nface0,
                     pmmg_split_result *out) {
-  if (!ctx) {
-    fprintf(stderr, "[parmmg_host] no HIP context: the group split has no CPU fallback\n");
-    return 0;
-  }
+  if (!have_ctx(ctx, "the group split")) return 0;
   if (!out) return 0;
   memset(out, 0, sizeof(*out));
   if (np < 0 || ne < 0 || ngrp < 1 || nfield < 0 || (nfield > 0 && (!field_size || !fields)) ||
@@ -483,117 +427,72 @@ int pmmg_split_grps(pmmg_hip_ctx *ctx, int np, const double *xyz, int ne, const 
     return 0;
   if (!met) met_size = 0;
   const int64_t nt = ne, i4 = (int64_t)sizeof(int), d8 = (int64_t)sizeof(double);
-  enum { D_TETV, D_ADJA, D_PART, D_NPOS, D_FOLD, D_XYZ, D_MET, D_OLDT, D_NEWT, D_TV, D_AD, D_OLDP, D_F1, D_F2, D_N1, D_N2,
-         D_ROWS, D_COUNT };
-  void *d[D_COUNT] = {NULL};
-  void **d_fields = NULL;
-  int ok = 1;
-#define UP(slot, src, bytes)                                                                   \
-  do {                                                                                         \
-    if (ok && (src) && (bytes) > 0) {                                                          \
-      d[slot] = pmmg_hip_malloc(ctx, (int64_t)(bytes));                                        \
-      ok = d[slot] != NULL && pmmg_hip_memcpy_h2d(ctx, d[slot], (src), (int64_t)(bytes));      \
-    }                                                                                          \
-  } while (0)
-#define ROOM(slot, bytes)                                                                      \
-  do {                                                                                         \
-    if (ok) ok = (d[slot] = pmmg_hip_malloc(ctx, (int64_t)(bytes) > 0 ? (int64_t)(bytes) : 16)) != NULL; \
-  } while (0)
-  UP(D_TETV, tetv, i4 * 4 * nt);
-  UP(D_ADJA, adja, i4 * 4 * nt);
-  UP(D_PART, part, i4 * nt);
-  UP(D_NPOS, node_pos, i4 * np);
-  UP(D_FOLD, face_old, i4 * 4 * nt);
-  ROOM(D_OLDT, i4 * nt);
-  ROOM(D_NEWT, i4 * nt);
-  ROOM(D_TV, i4 * 4 * nt);
-  ROOM(D_AD, i4 * 4 * nt);
+  pmmg_stage st = pmmg_stage_begin(ctx);
+  const int *d_tetv = pmmg_stage_up(&st, tetv, i4 * 4 * nt), *d_adja = pmmg_stage_up(&st, adja, i4 * 4 * nt);
+  const int *d_part = pmmg_stage_up(&st, part, i4 * nt), *d_npos = pmmg_stage_up(&st, node_pos, i4 * np);
+  const int *d_fold = pmmg_stage_up(&st, face_old, i4 * 4 * nt);
+  int *d_oldt = pmmg_stage_room(&st, i4 * nt), *d_newt = pmmg_stage_room(&st, i4 * nt);
+  int *d_tv = pmmg_stage_room(&st, i4 * 4 * nt), *d_ad = pmmg_stage_room(&st, i4 * 4 * nt);
   out->count = (pmmg_hip_split_count *)calloc((size_t)ngrp, sizeof(pmmg_hip_split_count));
-  ok = ok && out->count;
+  if (!out->count) st.ok = 0;
   /* caps of 0 size the lists: that call returns 0 with the counts filled unless every list is empty */
   int sized = 0;
-  if (ok)
-    sized = pmmg_hip_split_groups(ctx, np, ne, (const int *)d[D_TETV], (const int *)d[D_ADJA], NULL,
-                                  (const int *)d[D_PART], ngrp, (const int *)d[D_NPOS], (const int *)d[D_FOLD], nnode0,
-                                  nface0, out->count, 0, 0, 0, (int *)d[D_OLDT], (int *)d[D_NEWT], (int *)d[D_TV],
-                                  (int *)d[D_AD], NULL, NULL, NULL, NULL, NULL, NULL, &out->nnode_end, &out->nface_end);
+  if (st.ok)
+    sized = pmmg_hip_split_groups(ctx, np, ne, d_tetv, d_adja, NULL, d_part, ngrp, d_npos, d_fold, nnode0, nface0,
+                                  out->count, 0, 0, 0, d_oldt, d_newt, d_tv, d_ad, NULL, NULL, NULL, NULL, NULL, NULL,
+                                  &out->nnode_end, &out->nface_end);
   int64_t tot_ne = 0;
-  for (int g = 0; ok && g < ngrp; g++) {
+  for (int g = 0; st.ok && g < ngrp; g++) {
     tot_ne += out->count[g].ne;
     out->npt += out->count[g].np;
     out->nface += out->count[g].nface;
     out->nnode += out->count[g].nnode;
   }
-  if (ok && !sized && tot_ne != nt) ok = 0; /* a refusal: the counts were left at 0 */
-  ROOM(D_OLDP, i4 * out->npt);
-  ROOM(D_F1, i4 * out->nface);
-  ROOM(D_F2, i4 * out->nface);
-  ROOM(D_N1, i4 * out->nnode);
-  ROOM(D_N2, i4 * out->nnode);
-  if (ok && !sized)
-    ok = pmmg_hip_split_groups(ctx, np, ne, (const int *)d[D_TETV], (const int *)d[D_ADJA], NULL,
-                               (const int *)d[D_PART], ngrp, (const int *)d[D_NPOS], (const int *)d[D_FOLD], nnode0,
-                               nface0, out->count, out->npt, out->nface, out->nnode, (int *)d[D_OLDT],
-                               (int *)d[D_NEWT], (int *)d[D_TV], (int *)d[D_AD], NULL, (int *)d[D_OLDP], (int *)d[D_F1],
-                               (int *)d[D_F2], (int *)d[D_N1], (int *)d[D_N2], &out->nnode_end, &out->nface_end);
+  if (!sized && tot_ne != nt) st.ok = 0; /* a refusal: the counts were left at 0 */
+  int *d_oldp = pmmg_stage_room(&st, i4 * out->npt);
+  int *d_f1 = pmmg_stage_room(&st, i4 * out->nface), *d_f2 = pmmg_stage_room(&st, i4 * out->nface);
+  int *d_n1 = pmmg_stage_room(&st, i4 * out->nnode), *d_n2 = pmmg_stage_room(&st, i4 * out->nnode);
+  if (st.ok && !sized)
+    st.ok = pmmg_hip_split_groups(ctx, np, ne, d_tetv, d_adja, NULL, d_part, ngrp, d_npos, d_fold, nnode0, nface0,
+                                  out->count, out->npt, out->nface, out->nnode, d_oldt, d_newt, d_tv, d_ad, NULL,
+                                  d_oldp, d_f1, d_f2, d_n1, d_n2, &out->nnode_end, &out->nface_end);
   /* the point rows through old_pt: xyz, the metric, every field, one after the other through one device block */
   int width = met_size > 3 ? met_size : 3;
   for (int i = 0; i < nfield; i++)
     if (field_size[i] > width) width = field_size[i];
-  UP(D_XYZ, xyz, d8 * 3 * np);
-  ROOM(D_ROWS, d8 * width * out->npt);
-  if (ok) ok = pmmg_hip_gather_rows(ctx, out->npt, (const int *)d[D_OLDP], 3, (const double *)d[D_XYZ], (double *)d[D_ROWS]);
-  if (ok) ok = (out->xyz = (double *)split_down(ctx, d[D_ROWS], d8 * 3 * out->npt)) != NULL;
-  if (met_size) {
-    UP(D_MET, met, d8 * met_size * np);
-    if (ok)
-      ok = pmmg_hip_gather_rows(ctx, out->npt, (const int *)d[D_OLDP], met_size, (const double *)d[D_MET],
-                                (double *)d[D_ROWS]);
-    if (ok) ok = (out->met = (double *)split_down(ctx, d[D_ROWS], d8 * met_size * out->npt)) != NULL;
-  }
+  const double *d_xyz = pmmg_stage_up(&st, xyz, d8 * 3 * np);
+  double *rows = pmmg_stage_room(&st, d8 * width * out->npt);
+  out->xyz = pmmg_stage_rows(&st, out->npt, d_oldp, 3, d_xyz, rows);
+  if (met_size)
+    out->met = pmmg_stage_rows(&st, out->npt, d_oldp, met_size, pmmg_stage_up(&st, met, d8 * met_size * np), rows);
   out->met_size = met_size;
-  if (ok && nfield) {
+  if (st.ok && nfield) {
     out->fields = (double **)calloc((size_t)nfield, sizeof(double *));
-    d_fields = (void **)calloc((size_t)nfield, sizeof(void *));
-    ok = out->fields && d_fields;
-    out->nfield = ok ? nfield : 0;
+    if (out->fields)
+      out->nfield = nfield;
+    else
+      st.ok = 0;
   }
-  for (int i = 0; ok && i < nfield; i++) {
-    const int64_t bytes = d8 * field_size[i] * np;
+  for (int i = 0; st.ok && i < nfield; i++) {
     if (field_size[i] < 1 || !fields[i]) {
-      ok = 0;
+      st.ok = 0;
       break;
     }
-    if (bytes > 0) {
-      d_fields[i] = pmmg_hip_malloc(ctx, bytes);
-      ok = d_fields[i] != NULL && pmmg_hip_memcpy_h2d(ctx, d_fields[i], fields[i], bytes);
-    }
-    if (ok)
-      ok = pmmg_hip_gather_rows(ctx, out->npt, (const int *)d[D_OLDP], field_size[i], (const double *)d_fields[i],
-                                (double *)d[D_ROWS]);
-    if (ok) ok = (out->fields[i] = (double *)split_down(ctx, d[D_ROWS], d8 * field_size[i] * out->npt)) != NULL;
+    const double *d_field = pmmg_stage_up(&st, fields[i], d8 * field_size[i] * np);
+    out->fields[i] = pmmg_stage_rows(&st, out->npt, d_oldp, field_size[i], d_field, rows);
   }
-#undef UP
-#undef ROOM
-  if (ok) {
-    ok = (out->old_tet = (int *)split_down(ctx, d[D_OLDT], i4 * nt)) != NULL &&
-         (out->new_tet = (int *)split_down(ctx, d[D_NEWT], i4 * nt)) != NULL &&
-         (out->tetv = (int *)split_down(ctx, d[D_TV], i4 * 4 * nt)) != NULL &&
-         (out->adja = (int *)split_down(ctx, d[D_AD], i4 * 4 * nt)) != NULL &&
-         (out->old_pt = (int *)split_down(ctx, d[D_OLDP], i4 * out->npt)) != NULL &&
-         (out->face_idx1 = (int *)split_down(ctx, d[D_F1], i4 * out->nface)) != NULL &&
-         (out->face_idx2 = (int *)split_down(ctx, d[D_F2], i4 * out->nface)) != NULL &&
-         (out->node_idx1 = (int *)split_down(ctx, d[D_N1], i4 * out->nnode)) != NULL &&
-         (out->node_idx2 = (int *)split_down(ctx, d[D_N2], i4 * out->nnode)) != NULL;
-  }
-  for (int i = 0; i < D_COUNT; i++)
-    if (d[i]) pmmg_hip_free(ctx, d[i]);
-  if (d_fields)
-    for (int i = 0; i < nfield; i++)
-      if (d_fields[i]) pmmg_hip_free(ctx, d_fields[i]);
-  free(d_fields);
-  if (!ok) pmmg_split_result_free(out);
-  return ok;
+  out->old_tet = pmmg_stage_down(&st, d_oldt, i4 * nt);
+  out->new_tet = pmmg_stage_down(&st, d_newt, i4 * nt);
+  out->tetv = pmmg_stage_down(&st, d_tv, i4 * 4 * nt);
+  out->adja = pmmg_stage_down(&st, d_ad, i4 * 4 * nt);
+  out->old_pt = pmmg_stage_down(&st, d_oldp, i4 * out->npt);
+  out->face_idx1 = pmmg_stage_down(&st, d_f1, i4 * out->nface);
+  out->face_idx2 = pmmg_stage_down(&st, d_f2, i4 * out->nface);
+  out->node_idx1 = pmmg_stage_down(&st, d_n1, i4 * out->nnode);
+  out->node_idx2 = pmmg_stage_down(&st, d_n2, i4 * out->nnode);
+  pmmg_stage_end(&st);
+  if (!st.ok) pmmg_split_result_free(out);
+  return st.ok;
 }
 
 /* ---------------------------------------------------------------- group merge */
@@ -610,10 +509,7 @@ int pmmg_merge_grps(pmmg_hip_ctx *ctx, int ngrp, const pmmg_hip_split_count *cou
                     const int *node_idx1, const int *node_idx2, const int *face_idx1, const int *face_idx2, int nnode,
                     int nface, const int *color, const double *xyz, int met_size, const double *met, const int *tref,
                     pmmg_merge_result *out) {
-  if (!ctx) {
-    fprintf(stderr, "[parmmg_host] no HIP context: the group merge has no CPU fallback\n");
-    return 0;
-  }
+  if (!have_ctx(ctx, "the group merge")) return 0;
   if (!out) return 0;
   memset(out, 0, sizeof(*out));
   if (ngrp < 1 || !count || nnode < 0 || nface < 0) return 0;
@@ -630,73 +526,39 @@ int pmmg_merge_grps(pmmg_hip_ctx *ctx, int ngrp, const pmmg_hip_split_count *cou
     return 0;
   if (!met) met_size = 0;
   const int64_t i4 = (int64_t)sizeof(int), d8 = (int64_t)sizeof(double);
-  enum { D_TETV, D_N1, D_N2, D_F1, D_F2, D_XYZ, D_MET, D_TREF, D_NEWP, D_NEWT, D_SRCP, D_SRCT, D_TV, D_MARK, D_NVAL,
-         D_FVAL, D_ROWS, D_TROW, D_COUNT };
-  void *d[D_COUNT] = {NULL};
-  int ok = 1;
-#define UP(slot, src, bytes)                                                                   \
-  do {                                                                                         \
-    if (ok && (src) && (bytes) > 0) {                                                          \
-      d[slot] = pmmg_hip_malloc(ctx, (int64_t)(bytes));                                        \
-      ok = d[slot] != NULL && pmmg_hip_memcpy_h2d(ctx, d[slot], (src), (int64_t)(bytes));      \
-    }                                                                                          \
-  } while (0)
-#define ROOM(slot, bytes)                                                                      \
-  do {                                                                                         \
-    if (ok) ok = (d[slot] = pmmg_hip_malloc(ctx, (int64_t)(bytes) > 0 ? (int64_t)(bytes) : 16)) != NULL; \
-  } while (0)
-  UP(D_TETV, tetv, i4 * 4 * nt);
-  UP(D_N1, node_idx1, i4 * nne);
-  UP(D_N2, node_idx2, i4 * nne);
-  UP(D_F1, face_idx1, i4 * nfe);
-  UP(D_F2, face_idx2, i4 * nfe);
-  ROOM(D_NEWP, i4 * npt);
-  ROOM(D_NEWT, i4 * nt);
-  ROOM(D_SRCP, i4 * npt); /* (the merged points are at most the groups') */
-  ROOM(D_SRCT, i4 * nt);
-  ROOM(D_TV, i4 * 4 * nt);
-  if (color) ROOM(D_MARK, i4 * nt);
-  ROOM(D_NVAL, i4 * nnode);
-  ROOM(D_FVAL, i4 * nface);
-  if (ok)
-    ok = pmmg_hip_merge_groups(ctx, ngrp, count, (const int *)d[D_TETV], NULL, (const int *)d[D_N1],
-                               (const int *)d[D_N2], (const int *)d[D_F1], (const int *)d[D_F2], nnode, nface, color,
-                               npt, (int *)d[D_NEWP], (int *)d[D_NEWT], (int *)d[D_SRCP], (int *)d[D_SRCT],
-                               (int *)d[D_TV], (int *)d[D_MARK], (int *)d[D_NVAL], (int *)d[D_FVAL], &out->np, &out->ne);
+  pmmg_stage st = pmmg_stage_begin(ctx);
+  const int *d_tetv = pmmg_stage_up(&st, tetv, i4 * 4 * nt);
+  const int *d_n1 = pmmg_stage_up(&st, node_idx1, i4 * nne), *d_n2 = pmmg_stage_up(&st, node_idx2, i4 * nne);
+  const int *d_f1 = pmmg_stage_up(&st, face_idx1, i4 * nfe), *d_f2 = pmmg_stage_up(&st, face_idx2, i4 * nfe);
+  int *d_newp = pmmg_stage_room(&st, i4 * npt), *d_newt = pmmg_stage_room(&st, i4 * nt);
+  int *d_srcp = pmmg_stage_room(&st, i4 * npt); /* (the merged points are at most the groups') */
+  int *d_srct = pmmg_stage_room(&st, i4 * nt), *d_tv = pmmg_stage_room(&st, i4 * 4 * nt);
+  int *d_mark = color ? pmmg_stage_room(&st, i4 * nt) : NULL;
+  int *d_nval = pmmg_stage_room(&st, i4 * nnode), *d_fval = pmmg_stage_room(&st, i4 * nface);
+  if (st.ok)
+    st.ok = pmmg_hip_merge_groups(ctx, ngrp, count, d_tetv, NULL, d_n1, d_n2, d_f1, d_f2, nnode, nface, color, npt,
+                                  d_newp, d_newt, d_srcp, d_srct, d_tv, d_mark, d_nval, d_fval, &out->np, &out->ne);
   /* the point rows through src_pt and the references through src_tet, through one device block */
   const int width = met_size > 3 ? met_size : 3;
-  UP(D_XYZ, xyz, d8 * 3 * npt);
-  ROOM(D_ROWS, d8 * width * (ok ? out->np : 0));
-  if (ok) ok = pmmg_hip_gather_rows(ctx, out->np, (const int *)d[D_SRCP], 3, (const double *)d[D_XYZ], (double *)d[D_ROWS]);
-  if (ok) ok = (out->xyz = (double *)split_down(ctx, d[D_ROWS], d8 * 3 * out->np)) != NULL;
-  if (met_size) {
-    UP(D_MET, met, d8 * met_size * npt);
-    if (ok)
-      ok = pmmg_hip_gather_rows(ctx, out->np, (const int *)d[D_SRCP], met_size, (const double *)d[D_MET],
-                                (double *)d[D_ROWS]);
-    if (ok) ok = (out->met = (double *)split_down(ctx, d[D_ROWS], d8 * met_size * out->np)) != NULL;
-  }
+  const double *d_xyz = pmmg_stage_up(&st, xyz, d8 * 3 * npt);
+  double *rows = pmmg_stage_room(&st, d8 * width * out->np);
+  out->xyz = pmmg_stage_rows(&st, out->np, d_srcp, 3, d_xyz, rows);
+  if (met_size)
+    out->met = pmmg_stage_rows(&st, out->np, d_srcp, met_size, pmmg_stage_up(&st, met, d8 * met_size * npt), rows);
   out->met_size = met_size;
   if (tref) {
-    UP(D_TREF, tref, i4 * nt);
-    ROOM(D_TROW, i4 * nt);
-    if (ok) ok = pmmg_hip_gather_rows_i32(ctx, nt, (const int *)d[D_SRCT], 1, (const int *)d[D_TREF], (int *)d[D_TROW]);
-    if (ok) ok = (out->tref = (int *)split_down(ctx, d[D_TROW], i4 * nt)) != NULL;
+    const int *d_tref = pmmg_stage_up(&st, tref, i4 * nt);
+    out->tref = pmmg_stage_rows_i32(&st, nt, d_srct, 1, d_tref, pmmg_stage_room(&st, i4 * nt));
   }
-#undef UP
-#undef ROOM
-  if (ok) {
-    ok = (out->new_pt = (int *)split_down(ctx, d[D_NEWP], i4 * npt)) != NULL &&
-         (out->src_pt = (int *)split_down(ctx, d[D_SRCP], i4 * out->np)) != NULL &&
-         (out->new_tet = (int *)split_down(ctx, d[D_NEWT], i4 * nt)) != NULL &&
-         (out->src_tet = (int *)split_down(ctx, d[D_SRCT], i4 * nt)) != NULL &&
-         (out->tetv = (int *)split_down(ctx, d[D_TV], i4 * 4 * nt)) != NULL &&
-         (!color || (out->mark = (int *)split_down(ctx, d[D_MARK], i4 * nt)) != NULL) &&
-         (out->node_val = (int *)split_down(ctx, d[D_NVAL], i4 * nnode)) != NULL &&
-         (out->face_val = (int *)split_down(ctx, d[D_FVAL], i4 * nface)) != NULL;
-  }
-  for (int i = 0; i < D_COUNT; i++)
-    if (d[i]) pmmg_hip_free(ctx, d[i]);
-  if (!ok) pmmg_merge_result_free(out);
-  return ok;
+  out->new_pt = pmmg_stage_down(&st, d_newp, i4 * npt);
+  out->src_pt = pmmg_stage_down(&st, d_srcp, i4 * out->np);
+  out->new_tet = pmmg_stage_down(&st, d_newt, i4 * nt);
+  out->src_tet = pmmg_stage_down(&st, d_srct, i4 * nt);
+  out->tetv = pmmg_stage_down(&st, d_tv, i4 * 4 * nt);
+  if (color) out->mark = pmmg_stage_down(&st, d_mark, i4 * nt);
+  out->node_val = pmmg_stage_down(&st, d_nval, i4 * nnode);
+  out->face_val = pmmg_stage_down(&st, d_fval, i4 * nface);
+  pmmg_stage_end(&st);
+  if (!st.ok) pmmg_merge_result_free(out);
+  return st.ok;
 }

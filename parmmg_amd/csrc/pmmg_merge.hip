@@ -16,9 +16,9 @@
 // entry its position's word and (groups >= 1) its tetra's word, and adds one
 // to its face position's count.  Launch 2: the node entries that are their
 // point's first lower their position's word and add one to its holder count.
-// The atomics are agent scope, relaxed, without return, and a min is skipped
-// when a plain load already shows a lower value (pmmg_split.hip's scheme); a
-// word sees at most the groups that meet at its node or face.  No atomic
+// The atomics are agent scope, relaxed, without return, the minima guarded
+// (atomic_lower, pmmg_devutil.hpp); a word sees at most the groups that meet
+// at its node or face.  No atomic
 // touches a per-group or per-call word, and no kernel waits on another
 // workgroup's store.
 //
@@ -38,10 +38,6 @@
 #include "pmmg_tetview.hpp"
 
 namespace {
-
-constexpr int kMBlock = 256;
-constexpr int kMWaves = kMBlock / 64;
-constexpr int kMMaxBlocks = 2048; // grid-stride kernels: i + stride stays below 2^30 for lengths below 2^29
 
 typedef unsigned int u32;
 constexpr u32 kNoEntry = ~0u;
@@ -72,11 +68,6 @@ struct MOut {
   int *mark_out, *node_val, *face_val;
 };
 
-__device__ __forceinline__ void min32(u32 *p, u32 key) {
-  if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-    (void)__hip_atomic_fetch_min(p, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 __device__ __forceinline__ void add32(int *p) {
   (void)__hip_atomic_fetch_add(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -93,10 +84,10 @@ __device__ __forceinline__ int group_of(const int *off, int ngrp, int i) {
 }
 
 // The refusals.  Nothing is written but the flag word.
-__global__ __launch_bounds__(kMBlock) void k_merge_check(MView m, int n, int *flags) {
+__global__ __launch_bounds__(kPBlock) void k_merge_check(MView m, int n, int *flags) {
   int bad = 0;
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int i = (int)blockIdx.x * kMBlock + (int)threadIdx.x; i < n; i += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int i = (int)blockIdx.x * kPBlock + (int)threadIdx.x; i < n; i += stride) {
     if (i < m.T) {
       const int g = group_of(m.te_off, m.ngrp, i);
       const u32 npg = (u32)(m.pt_off[g + 1] - m.pt_off[g]);
@@ -119,23 +110,23 @@ __global__ __launch_bounds__(kMBlock) void k_merge_check(MView m, int n, int *fl
 }
 
 // Launch 1 of the lowest entries (the header of this file).
-__global__ __launch_bounds__(kMBlock) void k_merge_first(MView m, int n) {
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int e = (int)blockIdx.x * kMBlock + (int)threadIdx.x; e < n; e += stride) {
+__global__ __launch_bounds__(kPBlock) void k_merge_first(MView m, int n) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int e = (int)blockIdx.x * kPBlock + (int)threadIdx.x; e < n; e += stride) {
     if (e < m.En) {
       if (e < m.no_off[1]) {
-        min32(&m.posmin[m.n2[e]], (u32)e);
+        atomic_lower(&m.posmin[m.n2[e]], (u32)e);
       } else {
         const int g = group_of(m.no_off, m.ngrp, e);
-        min32(&m.ptfirst[m.pt_off[g] + m.n1[e] - 1], (u32)e);
+        atomic_lower(&m.ptfirst[m.pt_off[g] + m.n1[e] - 1], (u32)e);
       }
     }
     if (e < m.Ef) {
       const int q = m.f2[e];
-      min32(&m.fmin[q], (u32)e);
+      atomic_lower(&m.fmin[q], (u32)e);
       if (e >= m.fa_off[1]) {
         const int g = group_of(m.fa_off, m.ngrp, e);
-        min32(&m.tetfirst[m.te_off[g] + m.f1[e] / 12 - 1], (u32)e);
+        atomic_lower(&m.tetfirst[m.te_off[g] + m.f1[e] / 12 - 1], (u32)e);
         add32(&m.fcnt[q]);
       }
     }
@@ -143,13 +134,13 @@ __global__ __launch_bounds__(kMBlock) void k_merge_first(MView m, int n) {
 }
 
 // Launch 2: a point's first entry holds its position.
-__global__ __launch_bounds__(kMBlock) void k_merge_pos(MView m) {
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int e = m.no_off[1] + (int)blockIdx.x * kMBlock + (int)threadIdx.x; e < m.En; e += stride) {
+__global__ __launch_bounds__(kPBlock) void k_merge_pos(MView m) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int e = m.no_off[1] + (int)blockIdx.x * kPBlock + (int)threadIdx.x; e < m.En; e += stride) {
     const int g = group_of(m.no_off, m.ngrp, e);
     if (m.ptfirst[m.pt_off[g] + m.n1[e] - 1] != (u32)e) continue;
     const int p = m.n2[e];
-    min32(&m.posmin[p], (u32)e);
+    atomic_lower(&m.posmin[p], (u32)e);
     add32(&m.hold[p]);
   }
 }
@@ -183,21 +174,21 @@ __device__ __forceinline__ int flag_of(const MView &m, int d, int i) {
 }
 
 // btot[b] = the flags of block b
-__global__ __launch_bounds__(kMBlock) void k_merge_counts(MView m, int *btot) {
-  __shared__ int wt[kMWaves];
+__global__ __launch_bounds__(kPBlock) void k_merge_counts(MView m, int *btot) {
+  __shared__ int wt[kPWaves];
   const int b = (int)blockIdx.x, d = range_of(m, b);
-  const int i = (b - range_first(m, d)) * kMBlock + (int)threadIdx.x;
-  const int t = block_reduce<kMWaves>(flag_of(m, d, i), wt, IntSum());
+  const int i = (b - range_first(m, d)) * kPBlock + (int)threadIdx.x;
+  const int t = block_reduce<kPWaves>(flag_of(m, d, i), wt, IntSum());
   if (threadIdx.x == 0) btot[b] = t;
 }
 
 // pre[i] = the flags of the range before i; pre[length] = all of them
-__global__ __launch_bounds__(kMBlock) void k_merge_prefix(MView m, const int *boff) {
-  __shared__ int wt[kMWaves];
+__global__ __launch_bounds__(kPBlock) void k_merge_prefix(MView m, const int *boff) {
+  __shared__ int wt[kPWaves];
   const int b = (int)blockIdx.x, d = range_of(m, b), b0 = range_first(m, d);
-  const int i = (b - b0) * kMBlock + (int)threadIdx.x;
+  const int i = (b - b0) * kPBlock + (int)threadIdx.x;
   int tot;
-  const int p = block_prefix<kMWaves>(flag_of(m, d, i), wt, &tot);
+  const int p = block_prefix<kPWaves>(flag_of(m, d, i), wt, &tot);
   if (i <= range_len(m, d)) range_pre(m, d)[i] = boff[b] - boff[b0] + p;
 }
 
@@ -216,10 +207,10 @@ __device__ __forceinline__ int merged_tet(const MView &m, int t, int g) {
 }
 
 // new_pt, src_pt, node_val
-__global__ __launch_bounds__(kMBlock) void k_merge_points(MView m, MOut o, int n) {
+__global__ __launch_bounds__(kPBlock) void k_merge_points(MView m, MOut o, int n) {
   const int np0 = m.pt_off[1], ncre = m.pre_cre[m.En];
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int i = (int)blockIdx.x * kMBlock + (int)threadIdx.x; i < n; i += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int i = (int)blockIdx.x * kPBlock + (int)threadIdx.x; i < n; i += stride) {
     if (i < m.P) {
       int id;
       bool mine = true; // this point is the merged point's source
@@ -252,9 +243,9 @@ __global__ __launch_bounds__(kMBlock) void k_merge_points(MView m, MOut o, int n
 }
 
 // new_tet, src_tet, tetv_out, mark_out, face_val (after k_merge_points: the corners go through new_pt)
-__global__ __launch_bounds__(kMBlock) void k_merge_tetra(MView m, MOut o, int n) {
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int i = (int)blockIdx.x * kMBlock + (int)threadIdx.x; i < n; i += stride) {
+__global__ __launch_bounds__(kPBlock) void k_merge_tetra(MView m, MOut o, int n) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int i = (int)blockIdx.x * kPBlock + (int)threadIdx.x; i < n; i += stride) {
     if (i < m.T) {
       const int g = group_of(m.te_off, m.ngrp, i);
       const int id = merged_tet(m, i, g);
@@ -286,22 +277,6 @@ __global__ __launch_bounds__(kMBlock) void k_merge_tetra(MView m, MOut o, int n)
   }
 }
 
-// out row r = in row src[r] - 1 in pieces of T (4 or 16 bytes), `per` pieces a row
-template <class T>
-__global__ __launch_bounds__(kMBlock) void k_merge_gather(long long total, int per, const int *src, const T *in, T *out) {
-  const long long stride = (long long)gridDim.x * kMBlock;
-  for (long long i = (long long)blockIdx.x * kMBlock + threadIdx.x; i < total; i += stride) {
-    const long long r = i / per;
-    const int e = (int)(i - r * per);
-    out[i] = in[(long long)(src[r] - 1) * per + e];
-  }
-}
-
-int grid_for(long long n) {
-  const long long b = (n + kMBlock - 1) / kMBlock;
-  return b < 1 ? 1 : (b > kMMaxBlocks ? kMMaxBlocks : (int)b);
-}
-
 int max_of(int a, int b) { return a > b ? a : b; }
 
 } // namespace
@@ -327,7 +302,7 @@ int pmmg_merge_groups(hipStream_t s, const MergeArgs &a, MergeCache *c, char *ms
     return 0;
   }
   // the four ranges of the counts, each one item longer than its entries, in blocks
-  const int nb[D_KINDS] = {En / kMBlock + 1, P / kMBlock + 1, Ef / kMBlock + 1, T / kMBlock + 1};
+  const int nb[D_KINDS] = {En / kPBlock + 1, P / kPBlock + 1, Ef / kPBlock + 1, T / kPBlock + 1};
   const int nblk = nb[0] + nb[1] + nb[2] + nb[3];
   if (!reserve(c->blocks, nblk, s, "merge_groups: out of device memory (block counts)", msg, msglen)) return 0;
 
@@ -348,7 +323,7 @@ int pmmg_merge_groups(hipStream_t s, const MergeArgs &a, MergeCache *c, char *ms
   DEVCK(hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
   DEVCK(hipMemsetAsync(words, 0, 4 * sizeof(int), s));
   const int ncheck = max_of(T, max_of(En, Ef));
-  hipLaunchKernelGGL(k_merge_check, dim3(grid_for(ncheck)), dim3(kMBlock), 0, s, m, ncheck, words);
+  hipLaunchKernelGGL(k_merge_check, dim3(grid_for(ncheck)), dim3(kPBlock), 0, s, m, ncheck, words);
   DEVCK(hipGetLastError());
   int f = 0;
   if (!read_word(s, words, &f, msg, msglen)) return 0;
@@ -370,12 +345,12 @@ int pmmg_merge_groups(hipStream_t s, const MergeArgs &a, MergeCache *c, char *ms
   DEVCK(hipMemsetAsync(firsts, 0xff, sizeof(u32) * nfirst, s));
   DEVCK(hipMemsetAsync(counts, 0, sizeof(int) * ncount, s));
   const int nent = max_of(En, Ef);
-  hipLaunchKernelGGL(k_merge_first, dim3(grid_for(nent)), dim3(kMBlock), 0, s, m, nent);
-  hipLaunchKernelGGL(k_merge_pos, dim3(grid_for(En)), dim3(kMBlock), 0, s, m);
-  hipLaunchKernelGGL(k_merge_counts, dim3(nblk), dim3(kMBlock), 0, s, m, c->blocks.btot.as<int>());
+  hipLaunchKernelGGL(k_merge_first, dim3(grid_for(nent)), dim3(kPBlock), 0, s, m, nent);
+  hipLaunchKernelGGL(k_merge_pos, dim3(grid_for(En)), dim3(kPBlock), 0, s, m);
+  hipLaunchKernelGGL(k_merge_counts, dim3(nblk), dim3(kPBlock), 0, s, m, c->blocks.btot.as<int>());
   DEVCK(hipGetLastError());
   if (!offsets(c->blocks, s, nblk, nullptr, msg, msglen)) return 0;
-  hipLaunchKernelGGL(k_merge_prefix, dim3(nblk), dim3(kMBlock), 0, s, m, c->blocks.boff.as<int>());
+  hipLaunchKernelGGL(k_merge_prefix, dim3(nblk), dim3(kPBlock), 0, s, m, c->blocks.boff.as<int>());
   DEVCK(hipGetLastError());
   int ncre = 0, nunl = 0;
   DEVCK(hipMemcpyAsync(&ncre, m.pre_cre + En, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -394,24 +369,9 @@ int pmmg_merge_groups(hipStream_t s, const MergeArgs &a, MergeCache *c, char *ms
   const MOut o{a.new_pt, a.new_tet, a.src_pt, a.src_tet, reinterpret_cast<int4 *>(a.tetv_out),
                a.mark_out, a.node_val, a.face_val};
   const int npts = max_of(P, a.node_val ? nnode : 0), ntet = max_of(T, a.face_val ? nface : 0);
-  hipLaunchKernelGGL(k_merge_points, dim3(grid_for(npts)), dim3(kMBlock), 0, s, m, o, npts);
-  hipLaunchKernelGGL(k_merge_tetra, dim3(grid_for(ntet)), dim3(kMBlock), 0, s, m, o, ntet);
+  hipLaunchKernelGGL(k_merge_points, dim3(grid_for(npts)), dim3(kPBlock), 0, s, m, o, npts);
+  hipLaunchKernelGGL(k_merge_tetra, dim3(grid_for(ntet)), dim3(kPBlock), 0, s, m, o, ntet);
   DEVCK(hipGetLastError());
   DEVCK(hipStreamSynchronize(s));
-  return 1;
-}
-
-int pmmg_merge_gather_i32(hipStream_t s, int64_t n, const int *src, int size, const int *in, int *out, char *msg,
-                          size_t msglen) {
-  if (n == 0) return 1;
-  if (size % 4 == 0 && aligned<16>(in) && aligned<16>(out)) {
-    const long long total = (long long)n * (size / 4);
-    hipLaunchKernelGGL(k_merge_gather<int4>, dim3(grid_for(total)), dim3(kMBlock), 0, s, total, size / 4, src,
-                       reinterpret_cast<const int4 *>(in), reinterpret_cast<int4 *>(out));
-  } else {
-    const long long total = (long long)n * size;
-    hipLaunchKernelGGL(k_merge_gather<int>, dim3(grid_for(total)), dim3(kMBlock), 0, s, total, size, src, in, out);
-  }
-  DEVCK(hipGetLastError());
   return 1;
 }

@@ -35,7 +35,3 @@ struct MergeArgs {
   int *np_out, *ne_out;
 };
 int pmmg_merge_groups(hipStream_t s, const MergeArgs &a, MergeCache *cache, char *msg, size_t msglen);
-
-// out row r = in row src[r] - 1, rows of `size` ints.  Asynchronous on s.  Returns 1, or 0 with msg set.
-int pmmg_merge_gather_i32(hipStream_t s, int64_t n, const int *src, int size, const int *in, int *out, char *msg,
-                          size_t msglen);

@@ -10,14 +10,14 @@
 //
 // Seed.  Every corner 4 k + c of a used tetra lowers two 64-bit words of its
 // point: the corner itself, and (weight of the tetra's mark << 32 | corner)
-// (atomicMin, agent scope, relaxed, no return).  A pass over the points reads
+// (atomic_lower, pmmg_devutil.hpp).  A pass over the points reads
 // the colour and the front flag off the two words.
 //
 // A layer works on copies and is committed as a whole or not at all:
 //   k_ifc_sweep    per tetra: its front points in ascending id (a sorting
 //                  network in registers), the running strict minimum of weight,
 //                  the events; the new mark; per event the previous colour's
-//                  count in a table in LDS, flushed once per block and colour;
+//                  count in a CountTable in LDS, flushed once per block and colour;
 //                  the points off the front get (weight << 32 | point of the
 //                  last event) by atomicMin, the other front points a plain
 //                  store of 1 in `side`
@@ -41,10 +41,8 @@
 
 namespace {
 
-constexpr int kMBlock = 256;
-constexpr int kMMaxBlocks = 2048; // grid-stride kernels: k + stride stays below 2^30 for ne < 2^29
-constexpr int kMSlots = 1024;     // LDS table of a block: events per previous colour
-constexpr int kMProbe = 8;        // slots tried before a count goes to the global word directly
+// the events of a block per previous colour: 1024 slots, 8 tried before a count goes to the colour's word directly
+typedef CountTable<1024, 8> EventTable;
 
 typedef unsigned long long u64;
 constexpr u64 kNone = ~0ULL;
@@ -54,24 +52,17 @@ enum { I_BADMARK = 1, I_BADVERT = 2, I_BADCOLOR = 4, I_BADSET = 8, I_BADSETCOLOR
 // the calls' words on the device
 enum { W_FLAGS = 0, W_MOVED = 1, W_COUNT = 4 };
 
-__device__ __forceinline__ void min64(u64 *p, u64 key) {
-  if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-    (void)__hip_atomic_fetch_min(p, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-struct MMesh {
-  int ne, np;
-  const int4 *tetv;
-  int tstride;
+struct MMesh : TetRows {
+  int np;
 };
 
 // The refusals of a mesh with marks: a mark of a used tetra outside [0, ncolor), a vertex id outside [1, np];
 // with ptcolor, a point of a used tetra whose colour lies outside [0, ncolor).
-__global__ __launch_bounds__(kMBlock) void k_ifc_check(MMesh m, const int *mark, int ncolor, const int *ptcolor,
+__global__ __launch_bounds__(kPBlock) void k_ifc_check(MMesh m, const int *mark, int ncolor, const int *ptcolor,
                                                        int *flags) {
   int bad = 0;
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int k = (int)blockIdx.x * kMBlock + (int)threadIdx.x; k < m.ne; k += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < m.ne; k += stride) {
     const int4 v = m.tetv[(size_t)k * m.tstride];
     if (v.x <= 0) continue;
     if ((unsigned int)mark[k] >= (unsigned int)ncolor) bad |= I_BADMARK;
@@ -87,9 +78,9 @@ __global__ __launch_bounds__(kMBlock) void k_ifc_check(MMesh m, const int *mark,
   if (bad) atomicOr(flags, bad);
 }
 
-__global__ __launch_bounds__(kMBlock) void k_ifc_check_set(int np, int ncolor, int nset, const int *set_pt,
+__global__ __launch_bounds__(kPBlock) void k_ifc_check_set(int np, int ncolor, int nset, const int *set_pt,
                                                            const int *set_color, int *flags) {
-  const int i = (int)blockIdx.x * kMBlock + (int)threadIdx.x;
+  const int i = (int)blockIdx.x * kPBlock + (int)threadIdx.x;
   if (i >= nset) return;
   int bad = 0;
   if ((unsigned int)(set_pt[i] - 1) >= (unsigned int)np) bad |= I_BADSET;
@@ -99,10 +90,10 @@ __global__ __launch_bounds__(kMBlock) void k_ifc_check_set(int np, int ncolor, i
 
 // ---- the seed
 
-__global__ __launch_bounds__(kMBlock) void k_ifc_seed_min(MMesh m, const int *mark, const int *weight, u64 *first,
+__global__ __launch_bounds__(kPBlock) void k_ifc_seed_min(MMesh m, const int *mark, const int *weight, u64 *first,
                                                           u64 *best) {
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int k = (int)blockIdx.x * kMBlock + (int)threadIdx.x; k < m.ne; k += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < m.ne; k += stride) {
     const int4 v = m.tetv[(size_t)k * m.tstride];
     if (v.x <= 0) continue;
     const int vv[4] = {v.x, v.y, v.z, v.w};
@@ -110,17 +101,17 @@ __global__ __launch_bounds__(kMBlock) void k_ifc_seed_min(MMesh m, const int *ma
 #pragma unroll
     for (int c = 0; c < 4; c++) {
       const u64 corner = (u64)(unsigned int)(4 * k + c);
-      min64(&first[vv[c] - 1], corner);
-      min64(&best[vv[c] - 1], wk | corner);
+      atomic_lower(&first[vv[c] - 1], corner);
+      atomic_lower(&best[vv[c] - 1], wk | corner);
     }
   }
 }
 
-__global__ __launch_bounds__(kMBlock) void k_ifc_seed_points(int np, const int *mark, const int *weight,
+__global__ __launch_bounds__(kPBlock) void k_ifc_seed_points(int np, const int *mark, const int *weight,
                                                              const u64 *first, const u64 *best, int *ptcolor,
                                                              unsigned char *ptfront) {
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int p = (int)blockIdx.x * kMBlock + (int)threadIdx.x; p < np; p += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int p = (int)blockIdx.x * kPBlock + (int)threadIdx.x; p < np; p += stride) {
     const u64 f = first[p], b = best[p];
     if (f == kNone) { // in no used tetra
       ptcolor[p] = -1;
@@ -136,9 +127,9 @@ __global__ __launch_bounds__(kMBlock) void k_ifc_seed_points(int np, const int *
 
 // The set points of a layer become front (and take their colours); what they held is kept for a layer that is
 // dropped.  The entries of set_pt are distinct.
-__global__ __launch_bounds__(kMBlock) void k_ifc_set(int nset, const int *set_pt, const int *set_color, int *color,
+__global__ __launch_bounds__(kPBlock) void k_ifc_set(int nset, const int *set_pt, const int *set_color, int *color,
                                                      unsigned char *front, int *old_color, unsigned char *old_front) {
-  const int i = (int)blockIdx.x * kMBlock + (int)threadIdx.x;
+  const int i = (int)blockIdx.x * kPBlock + (int)threadIdx.x;
   if (i >= nset) return;
   const int p = set_pt[i] - 1;
   old_color[i] = color[p];
@@ -147,28 +138,14 @@ __global__ __launch_bounds__(kMBlock) void k_ifc_set(int nset, const int *set_pt
   if (set_color) color[p] = set_color[i];
 }
 
-__global__ __launch_bounds__(kMBlock) void k_ifc_unset(int nset, const int *set_pt, const int *old_color,
+__global__ __launch_bounds__(kPBlock) void k_ifc_unset(int nset, const int *set_pt, const int *old_color,
                                                        const unsigned char *old_front, int *color,
                                                        unsigned char *front) {
-  const int i = (int)blockIdx.x * kMBlock + (int)threadIdx.x;
+  const int i = (int)blockIdx.x * kPBlock + (int)threadIdx.x;
   if (i >= nset) return;
   const int p = set_pt[i] - 1;
   color[p] = old_color[i];
   front[p] = old_front[i];
-}
-
-// one more event with previous colour g: the block's table, or after kMProbe occupied slots the global word
-__device__ __forceinline__ void event_add(int *s_key, int *s_cnt, int *D, int g) {
-  unsigned int h = ((unsigned int)g * 2654435761u) >> 22;
-  for (int i = 0; i < kMProbe; i++) {
-    const int old = atomicCAS(&s_key[h], -1, g);
-    if (old == -1 || old == g) {
-      atomicAdd(&s_cnt[h], 1);
-      return;
-    }
-    h = (h + 1) & (kMSlots - 1);
-  }
-  atomicAdd(&D[g], 1);
 }
 
 __device__ __forceinline__ void cswap(int &a, int &b) {
@@ -177,20 +154,18 @@ __device__ __forceinline__ void cswap(int &a, int &b) {
   b = hi;
 }
 
-__global__ __launch_bounds__(kMBlock) void k_ifc_sweep(MMesh m, const int *mark, const int *weight, const int *color,
+__global__ __launch_bounds__(kPBlock) void k_ifc_sweep(MMesh m, const int *mark, const int *weight, const int *color,
                                                        const unsigned char *front, int *nmark, u64 *ekey,
                                                        unsigned char *side, int *D, int *moved) {
-  static_assert((kMSlots & (kMSlots - 1)) == 0 && kMSlots == 1 << 10, "the hash keeps 10 bits");
-  __shared__ int s_key[kMSlots], s_cnt[kMSlots], s_moved;
-  for (int i = (int)threadIdx.x; i < kMSlots; i += kMBlock) {
-    s_key[i] = -1;
-    s_cnt[i] = 0;
-  }
+  __shared__ EventTable events;
+  __shared__ int s_moved;
+  const auto count_of = [D](int g) { return &D[g]; };
+  events.clear<kPBlock>();
   if (threadIdx.x == 0) s_moved = 0;
   __syncthreads();
   int nmoved = 0;
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int k = (int)blockIdx.x * kMBlock + (int)threadIdx.x; k < m.ne; k += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < m.ne; k += stride) {
     const int4 v = m.tetv[(size_t)k * m.tstride];
     const int mk = mark[k];
     if (v.x <= 0) {
@@ -213,7 +188,7 @@ __global__ __launch_bounds__(kMBlock) void k_ifc_sweep(MMesh m, const int *mark,
       if (!fr[j]) continue;
       const int C = color[id[j] - 1], wc = weight[C];
       if (wc < curw) { // an event: C beats the running colour
-        event_add(s_key, s_cnt, D, cur);
+        events.add(cur, 1, count_of);
         cur = C;
         curw = wc;
         nev++;
@@ -227,22 +202,21 @@ __global__ __launch_bounds__(kMBlock) void k_ifc_sweep(MMesh m, const int *mark,
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       if (!fr[j])
-        min64(&ekey[id[j] - 1], key);
+        atomic_lower(&ekey[id[j] - 1], key);
       else if (nev > 1 || id[j] != last)
         side[id[j] - 1] = 1;
     }
   }
   if (nmoved) atomicAdd(&s_moved, nmoved);
   __syncthreads();
-  for (int i = (int)threadIdx.x; i < kMSlots; i += kMBlock)
-    if (s_key[i] >= 0) atomicAdd(&D[s_key[i]], s_cnt[i]);
+  events.flush<kPBlock>(count_of);
   if (threadIdx.x == 0 && s_moved) atomicAdd(moved, s_moved);
 }
 
-__global__ __launch_bounds__(kMBlock) void k_ifc_side(MMesh m, const int *nmark, const int *weight,
+__global__ __launch_bounds__(kPBlock) void k_ifc_side(MMesh m, const int *nmark, const int *weight,
                                                       const unsigned char *side, u64 *skey) {
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int k = (int)blockIdx.x * kMBlock + (int)threadIdx.x; k < m.ne; k += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < m.ne; k += stride) {
     const int4 v = m.tetv[(size_t)k * m.tstride];
     if (v.x <= 0) continue;
     const int vv[4] = {v.x, v.y, v.z, v.w};
@@ -253,15 +227,15 @@ __global__ __launch_bounds__(kMBlock) void k_ifc_side(MMesh m, const int *nmark,
     const u64 key = ((u64)(unsigned int)weight[nmark[k]] << 32) | (u64)(unsigned int)k;
 #pragma unroll
     for (int c = 0; c < 4; c++)
-      if (sd[c]) min64(&skey[vv[c] - 1], key);
+      if (sd[c]) atomic_lower(&skey[vv[c] - 1], key);
   }
 }
 
-__global__ __launch_bounds__(kMBlock) void k_ifc_points(int np, const int *nmark, const int *weight, const int *color,
+__global__ __launch_bounds__(kPBlock) void k_ifc_points(int np, const int *nmark, const int *weight, const int *color,
                                                         const u64 *ekey, const u64 *skey, const unsigned char *side,
                                                         int *ncolor_out, unsigned char *nfront) {
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int p = (int)blockIdx.x * kMBlock + (int)threadIdx.x; p < np; p += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int p = (int)blockIdx.x * kPBlock + (int)threadIdx.x; p < np; p += stride) {
     const int c = color[p];
     const u64 e = ekey[p];
     const bool sd = side[p] != 0;
@@ -281,11 +255,11 @@ __global__ __launch_bounds__(kMBlock) void k_ifc_points(int np, const int *nmark
 
 // ---- the packing of the colours
 
-__global__ __launch_bounds__(kMBlock) void k_ifc_present(MMesh m, const int *mark, int ncolor, unsigned char *present,
+__global__ __launch_bounds__(kPBlock) void k_ifc_present(MMesh m, const int *mark, int ncolor, unsigned char *present,
                                                          int *flags) {
   bool bad = false;
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int k = (int)blockIdx.x * kMBlock + (int)threadIdx.x; k < m.ne; k += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < m.ne; k += stride) {
     if (m.tetv[(size_t)k * m.tstride].x <= 0) continue;
     const int g = mark[k];
     if ((unsigned int)g >= (unsigned int)ncolor)
@@ -296,15 +270,10 @@ __global__ __launch_bounds__(kMBlock) void k_ifc_present(MMesh m, const int *mar
   if (bad) atomicOr(flags, (int)I_BADMARK);
 }
 
-__global__ __launch_bounds__(kMBlock) void k_ifc_apply(MMesh m, const int *mark, const int *map, int *part) {
-  const int stride = (int)gridDim.x * kMBlock;
-  for (int k = (int)blockIdx.x * kMBlock + (int)threadIdx.x; k < m.ne; k += stride)
+__global__ __launch_bounds__(kPBlock) void k_ifc_apply(MMesh m, const int *mark, const int *map, int *part) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < m.ne; k += stride)
     part[k] = m.tetv[(size_t)k * m.tstride].x <= 0 ? 0 : map[mark[k]];
-}
-
-int grid_for(long long n) {
-  const long long b = (n + kMBlock - 1) / kMBlock;
-  return b < 1 ? 1 : (b > kMMaxBlocks ? kMMaxBlocks : (int)b);
 }
 
 int bad_weight(int ncolor, const int *weight, const char *who, char *msg, size_t msglen) {
@@ -343,10 +312,10 @@ int pmmg_ifc_seed(hipStream_t s, int np, TetView tv, const int *mark, int ncolor
     snprintf(msg, msglen, "ifc_seed: out of device memory (scratch of %d points, %d colours)", np, ncolor);
     return 0;
   }
-  const MMesh m{ne, np, reinterpret_cast<const int4 *>(tv.tetv), tv.tstride};
+  const MMesh m{rows_of(tv), np};
   DEVCK(hipMemsetAsync(words, 0, W_COUNT * sizeof(int), s));
   if (ne > 0) {
-    hipLaunchKernelGGL(k_ifc_check, dim3(grid_for(ne)), dim3(kMBlock), 0, s, m, mark, ncolor, (const int *)nullptr,
+    hipLaunchKernelGGL(k_ifc_check, dim3(grid_for(ne)), dim3(kPBlock), 0, s, m, mark, ncolor, (const int *)nullptr,
                        words + W_FLAGS);
     DEVCK(hipGetLastError());
   }
@@ -357,8 +326,8 @@ int pmmg_ifc_seed(hipStream_t s, int np, TetView tv, const int *mark, int ncolor
   DEVCK(hipMemcpyAsync(wdev, weight, sizeof(int) * (size_t)ncolor, hipMemcpyHostToDevice, s));
   DEVCK(hipMemsetAsync(first, 0xff, sizeof(u64) * (size_t)np, s));
   DEVCK(hipMemsetAsync(best, 0xff, sizeof(u64) * (size_t)np, s));
-  if (ne > 0) hipLaunchKernelGGL(k_ifc_seed_min, dim3(grid_for(ne)), dim3(kMBlock), 0, s, m, mark, wdev, first, best);
-  hipLaunchKernelGGL(k_ifc_seed_points, dim3(grid_for(np)), dim3(kMBlock), 0, s, np, mark, wdev, first, best, ptcolor,
+  if (ne > 0) hipLaunchKernelGGL(k_ifc_seed_min, dim3(grid_for(ne)), dim3(kPBlock), 0, s, m, mark, wdev, first, best);
+  hipLaunchKernelGGL(k_ifc_seed_points, dim3(grid_for(np)), dim3(kPBlock), 0, s, np, mark, wdev, first, best, ptcolor,
                      ptfront);
   DEVCK(hipGetLastError());
   DEVCK(hipStreamSynchronize(s)); // (the copy of `weight`, a pageable host array, is done too)
@@ -386,14 +355,14 @@ int pmmg_ifc_layers(hipStream_t s, int np, TetView tv, int *mark, int ncolor, co
              ncolor);
     return 0;
   }
-  const MMesh m{ne, np, reinterpret_cast<const int4 *>(tv.tetv), tv.tstride};
-  const int grid = grid_for(ne), pgrid = grid_for(np), sgrid = (nset + kMBlock - 1) / kMBlock;
+  const MMesh m{rows_of(tv), np};
+  const int grid = grid_for(ne), pgrid = grid_for(np), sgrid = (nset + kPBlock - 1) / kPBlock;
 
   // the refusals: nothing is written to an output before they are known
   DEVCK(hipMemsetAsync(words, 0, W_COUNT * sizeof(int), s));
-  if (ne > 0) hipLaunchKernelGGL(k_ifc_check, dim3(grid), dim3(kMBlock), 0, s, m, mark, ncolor, ptcolor, words + W_FLAGS);
+  if (ne > 0) hipLaunchKernelGGL(k_ifc_check, dim3(grid), dim3(kPBlock), 0, s, m, mark, ncolor, ptcolor, words + W_FLAGS);
   if (nset > 0)
-    hipLaunchKernelGGL(k_ifc_check_set, dim3(sgrid), dim3(kMBlock), 0, s, np, ncolor, nset, set_pt, set_color,
+    hipLaunchKernelGGL(k_ifc_check_set, dim3(sgrid), dim3(kPBlock), 0, s, np, ncolor, nset, set_pt, set_color,
                        words + W_FLAGS);
   DEVCK(hipGetLastError());
   int f = 0;
@@ -423,17 +392,17 @@ int pmmg_ifc_layers(hipStream_t s, int np, TetView tv, int *mark, int ncolor, co
     int *nm = mk[wm], *nc = col[wp];
     unsigned char *nf = fr[wp];
     if (nset > 0) // (cc / cf are scratch copies here)
-      hipLaunchKernelGGL(k_ifc_set, dim3(sgrid), dim3(kMBlock), 0, s, nset, set_pt, l == 0 ? set_color : nullptr,
+      hipLaunchKernelGGL(k_ifc_set, dim3(sgrid), dim3(kPBlock), 0, s, nset, set_pt, l == 0 ? set_color : nullptr,
                          const_cast<int *>(cc), const_cast<unsigned char *>(cf), old_color, old_front);
     DEVCK(hipMemsetAsync(ekey, 0xff, sizeof(u64) * (size_t)np, s));
     DEVCK(hipMemsetAsync(skey, 0xff, sizeof(u64) * (size_t)np, s));
     DEVCK(hipMemsetAsync(side, 0, (size_t)np, s));
     DEVCK(hipMemsetAsync(D, 0, sizeof(int) * (size_t)ncolor, s));
     DEVCK(hipMemsetAsync(words + W_MOVED, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_ifc_sweep, dim3(grid), dim3(kMBlock), 0, s, m, cm, wdev, cc, cf, nm, ekey, side, D,
+    hipLaunchKernelGGL(k_ifc_sweep, dim3(grid), dim3(kPBlock), 0, s, m, cm, wdev, cc, cf, nm, ekey, side, D,
                        words + W_MOVED);
-    hipLaunchKernelGGL(k_ifc_side, dim3(grid), dim3(kMBlock), 0, s, m, nm, wdev, side, skey);
-    hipLaunchKernelGGL(k_ifc_points, dim3(pgrid), dim3(kMBlock), 0, s, np, nm, wdev, cc, ekey, skey, side, nc, nf);
+    hipLaunchKernelGGL(k_ifc_side, dim3(grid), dim3(kPBlock), 0, s, m, nm, wdev, side, skey);
+    hipLaunchKernelGGL(k_ifc_points, dim3(pgrid), dim3(kPBlock), 0, s, np, nm, wdev, cc, ekey, skey, side, nc, nf);
     DEVCK(hipGetLastError());
     int nmoved = 0;
     DEVCK(hipMemcpyAsync(hD.data(), D, sizeof(int) * (size_t)ncolor, hipMemcpyDeviceToHost, s));
@@ -442,7 +411,7 @@ int pmmg_ifc_layers(hipStream_t s, int np, TetView tv, int *mark, int ncolor, co
       // the layer is dropped, its set points with it: the outputs are the previous layer's
       *blocked = 1;
       if (nset > 0 && l > 0)
-        hipLaunchKernelGGL(k_ifc_unset, dim3(sgrid), dim3(kMBlock), 0, s, nset, set_pt, old_color, old_front,
+        hipLaunchKernelGGL(k_ifc_unset, dim3(sgrid), dim3(kPBlock), 0, s, nset, set_pt, old_color, old_front,
                            const_cast<int *>(cc), const_cast<unsigned char *>(cf));
       DEVCK(hipGetLastError());
       break;
@@ -481,10 +450,10 @@ int pmmg_ifc_remap(hipStream_t s, TetView tv, const int *mark, int ncolor, const
   }
   unsigned char *present = reinterpret_cast<unsigned char *>(buf);
   int *map = buf + pwords;
-  const MMesh m{ne, 0, reinterpret_cast<const int4 *>(tv.tetv), tv.tstride};
+  const MMesh m{rows_of(tv), 0};
   DEVCK(hipMemsetAsync(words, 0, W_COUNT * sizeof(int), s));
   DEVCK(hipMemsetAsync(present, 0, pwords * sizeof(int), s));
-  hipLaunchKernelGGL(k_ifc_present, dim3(grid_for(ne)), dim3(kMBlock), 0, s, m, mark, ncolor, present, words + W_FLAGS);
+  hipLaunchKernelGGL(k_ifc_present, dim3(grid_for(ne)), dim3(kPBlock), 0, s, m, mark, ncolor, present, words + W_FLAGS);
   DEVCK(hipGetLastError());
   std::vector<unsigned char> hp((size_t)ncolor);
   std::vector<int> hmap((size_t)ncolor);
@@ -494,7 +463,7 @@ int pmmg_ifc_remap(hipStream_t s, TetView tv, const int *mark, int ncolor, const
   if (refused(f, "remap_colors", ncolor, 0, msg, msglen)) return 0;
   *ngrp = ifc_pack_colors(ncolor, hp.data(), order, hmap.data());
   DEVCK(hipMemcpyAsync(map, hmap.data(), sizeof(int) * (size_t)ncolor, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_ifc_apply, dim3(grid_for(ne)), dim3(kMBlock), 0, s, m, mark, map, part);
+  hipLaunchKernelGGL(k_ifc_apply, dim3(grid_for(ne)), dim3(kPBlock), 0, s, m, mark, map, part);
   DEVCK(hipGetLastError());
   DEVCK(hipStreamSynchronize(s));
   return 1;

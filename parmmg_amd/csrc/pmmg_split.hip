@@ -12,9 +12,9 @@
 //
 // First use of a vertex in a group.  Rounds of two launches.  In a round every
 // corner that is not settled yet lowers its vertex's 64-bit word to
-// (colour << 32 | place) (atomicMin, agent scope, relaxed, no return; skipped
-// when the word read first is already lower); the next launch settles the corners whose colour
-// is the word's (first[place] = the word's place) and resets the other array's word of
+// (colour << 32 | place) (atomic_lower, pmmg_devutil.hpp); the next launch
+// settles the corners whose colour is the word's (first[place] = the word's
+// place) and resets the other array's word of
 // every vertex that still has an unsettled corner.  Round r settles, at every
 // vertex, its r-th lowest colour: interior vertices, the bulk, take one round,
 // and a tetra whose corners are settled leaves a later round after one 16-byte
@@ -38,10 +38,6 @@
 
 namespace {
 
-constexpr int kSBlock = 256;
-constexpr int kSWaves = kSBlock / 64;
-constexpr int kSMaxBlocks = 2048; // grid-stride kernels: n + stride stays below 2^30 for ne < 2^29
-
 typedef unsigned long long u64;
 constexpr u64 kNone = ~0ULL;
 constexpr int kNodeShift = 34; // 12 n + 11 < 2^34 for n < 2^29, and a colour below 2^29 stays in 63 bits
@@ -61,26 +57,17 @@ __device__ __forceinline__ constexpr int idir(int f, int p) {
 
 __device__ __forceinline__ int bits(unsigned int x) { return (int)__popc(x); }
 
-__device__ __forceinline__ void min64(u64 *p, u64 key) {
-  if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-    (void)__hip_atomic_fetch_min(p, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // what the passes read of the mesh
-struct SMesh {
-  int ne, np;
-  const int4 *tetv;
-  int tstride;
-  const int4 *adja;
-  int astride;
+struct SMesh : TetRows {
+  int np;
   const int *part;
 };
 
 // The refusals, and the sort's values 1 .. ne.
-__global__ __launch_bounds__(kSBlock) void k_split_check(SMesh m, int ngrp, int *iota, int *flags) {
+__global__ __launch_bounds__(kPBlock) void k_split_check(SMesh m, int ngrp, int *iota, int *flags) {
   int bad = 0;
-  const int stride = (int)gridDim.x * kSBlock;
-  for (int k = (int)blockIdx.x * kSBlock + (int)threadIdx.x; k < m.ne; k += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int k = (int)blockIdx.x * kPBlock + (int)threadIdx.x; k < m.ne; k += stride) {
     iota[k] = k + 1;
     if ((unsigned int)m.part[k] >= (unsigned int)ngrp) bad |= S_BADPART;
     const int4 v = m.tetv[(size_t)k * m.tstride];
@@ -105,7 +92,7 @@ __global__ __launch_bounds__(kSBlock) void k_split_check(SMesh m, int ngrp, int 
 // consecutive keys.  hist is digit-major, hist[digit * ntile + tile], so its exclusive scan is the first
 // output place of every (digit, tile).
 
-constexpr int kDigitItems = 8, kDigitTile = kSBlock * kDigitItems;
+constexpr int kDigitItems = 8, kDigitTile = kPBlock * kDigitItems;
 
 // the lanes of the wave whose (valid) key has this lane's digit
 __device__ __forceinline__ u64 same_digit(unsigned int d, bool ok) {
@@ -118,15 +105,15 @@ __device__ __forceinline__ u64 same_digit(unsigned int d, bool ok) {
   return same;
 }
 
-__global__ __launch_bounds__(kSBlock) void k_split_digit_count(int ne, int shift, int ntile, const int *keys, int *hist) {
-  static_assert(kSBlock == 256, "one thread per digit");
+__global__ __launch_bounds__(kPBlock) void k_split_digit_count(int ne, int shift, int ntile, const int *keys, int *hist) {
+  static_assert(kPBlock == 256, "one thread per digit");
   __shared__ int h[256];
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const u64 below = (1ULL << lane) - 1ULL;
   for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
     h[t] = 0;
     __syncthreads();
-    const long long base = (long long)tile * kDigitTile + w * (kDigitTile / kSWaves);
+    const long long base = (long long)tile * kDigitTile + w * (kDigitTile / kPWaves);
 #pragma unroll
     for (int j = 0; j < kDigitItems; j++) {
       const long long e = base + j * 64 + lane;
@@ -141,16 +128,16 @@ __global__ __launch_bounds__(kSBlock) void k_split_digit_count(int ne, int shift
   }
 }
 
-__global__ __launch_bounds__(kSBlock) void k_split_digit_scatter(int ne, int shift, int ntile, const int *off,
+__global__ __launch_bounds__(kPBlock) void k_split_digit_scatter(int ne, int shift, int ntile, const int *off,
                                                                  const int *kin, const int *vin, int *kout, int *vout) {
-  __shared__ int wdig[kSWaves][256]; // a wave's count per digit, then the first output place of its keys of the digit
+  __shared__ int wdig[kPWaves][256]; // a wave's count per digit, then the first output place of its keys of the digit
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const u64 below = (1ULL << lane) - 1ULL;
   for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
 #pragma unroll
-    for (int q = 0; q < kSWaves; q++) wdig[q][t] = 0;
+    for (int q = 0; q < kPWaves; q++) wdig[q][t] = 0;
     __syncthreads();
-    const long long base = (long long)tile * kDigitTile + w * (kDigitTile / kSWaves);
+    const long long base = (long long)tile * kDigitTile + w * (kDigitTile / kPWaves);
     int key[kDigitItems], val[kDigitItems], rk[kDigitItems];
 #pragma unroll
     for (int j = 0; j < kDigitItems; j++) {
@@ -173,7 +160,7 @@ __global__ __launch_bounds__(kSBlock) void k_split_digit_scatter(int ne, int shi
     __syncthreads();
     int acc = off[(size_t)t * ntile + tile];
 #pragma unroll
-    for (int q = 0; q < kSWaves; q++) {
+    for (int q = 0; q < kPWaves; q++) {
       const int c = wdig[q][t];
       wdig[q][t] = acc;
       acc += c;
@@ -193,10 +180,10 @@ __global__ __launch_bounds__(kSBlock) void k_split_digit_scatter(int ne, int shi
 
 // pos[old tetra] = its new place; teoff[g] = the first place of colour g (of the next colour that has tetra, or
 // ne).  The thread of a colour's first tetra writes the entries of the empty colours before it as well.
-__global__ __launch_bounds__(kSBlock) void k_split_places(int ne, int ngrp, const int *skey, const int *old_tet,
+__global__ __launch_bounds__(kPBlock) void k_split_places(int ne, int ngrp, const int *skey, const int *old_tet,
                                                           int *pos, int *teoff) {
-  const int stride = (int)gridDim.x * kSBlock;
-  for (int n = (int)blockIdx.x * kSBlock + (int)threadIdx.x; n < ne; n += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int n = (int)blockIdx.x * kPBlock + (int)threadIdx.x; n < ne; n += stride) {
     pos[old_tet[n] - 1] = n;
     const int g = skey[n], prev = n ? skey[n - 1] : -1;
     for (int c = prev + 1; c <= g; c++) teoff[c] = n;
@@ -206,10 +193,10 @@ __global__ __launch_bounds__(kSBlock) void k_split_places(int ne, int ngrp, cons
 }
 
 // A round's first launch: the unsettled corners lower their vertices' words.
-__global__ __launch_bounds__(kSBlock) void k_split_first_min(SMesh m, const int *skey, const int *old_tet,
+__global__ __launch_bounds__(kPBlock) void k_split_first_min(SMesh m, const int *skey, const int *old_tet,
                                                              const int4 *first, u64 *cur) {
-  const int stride = (int)gridDim.x * kSBlock;
-  for (int n = (int)blockIdx.x * kSBlock + (int)threadIdx.x; n < m.ne; n += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int n = (int)blockIdx.x * kPBlock + (int)threadIdx.x; n < m.ne; n += stride) {
     const int4 fr = first[n];
     if ((fr.x | fr.y | fr.z | fr.w) >= 0) continue;
     const int4 v = m.tetv[(size_t)(old_tet[n] - 1) * m.tstride];
@@ -217,17 +204,17 @@ __global__ __launch_bounds__(kSBlock) void k_split_first_min(SMesh m, const int 
     const u64 key = ((u64)(unsigned int)skey[n] << 32) | (u64)(unsigned int)(4 * n);
 #pragma unroll
     for (int c = 0; c < 4; c++)
-      if (ff[c] < 0) min64(&cur[vv[c] - 1], key + (u64)c);
+      if (ff[c] < 0) atomic_lower(&cur[vv[c] - 1], key + (u64)c);
   }
 }
 
 // A round's second launch: a corner whose colour is its vertex's word is settled; the vertex of one that is not
 // gets its word of the next round reset.  *left: a plain store of 1 by whoever stays unsettled.
-__global__ __launch_bounds__(kSBlock) void k_split_first_settle(SMesh m, const int *skey, const int *old_tet,
+__global__ __launch_bounds__(kPBlock) void k_split_first_settle(SMesh m, const int *skey, const int *old_tet,
                                                                 int4 *first, const u64 *cur, u64 *nxt, int *left) {
   bool l = false;
-  const int stride = (int)gridDim.x * kSBlock;
-  for (int n = (int)blockIdx.x * kSBlock + (int)threadIdx.x; n < m.ne; n += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int n = (int)blockIdx.x * kPBlock + (int)threadIdx.x; n < m.ne; n += stride) {
     const int4 fr = first[n];
     if ((fr.x | fr.y | fr.z | fr.w) >= 0) continue;
     const int4 v = m.tetv[(size_t)(old_tet[n] - 1) * m.tstride];
@@ -252,10 +239,10 @@ __global__ __launch_bounds__(kSBlock) void k_split_first_settle(SMesh m, const i
 
 // Per vertex without an old position: the lowest (colour, 12 n + 3 f + p) over the corners of the faces towards
 // another colour: its owner and its rank among the owner's new interface nodes.
-__global__ __launch_bounds__(kSBlock) void k_split_node_min(SMesh m, const int *skey, const int *old_tet,
+__global__ __launch_bounds__(kPBlock) void k_split_node_min(SMesh m, const int *skey, const int *old_tet,
                                                             const int *node_pos, u64 *nmin) {
-  const int stride = (int)gridDim.x * kSBlock;
-  for (int n = (int)blockIdx.x * kSBlock + (int)threadIdx.x; n < m.ne; n += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int n = (int)blockIdx.x * kPBlock + (int)threadIdx.x; n < m.ne; n += stride) {
     const int k = old_tet[n] - 1, g = skey[n];
     const int4 a = m.adja[(size_t)k * m.astride];
     const int lk[4] = {a.x, a.y, a.z, a.w};
@@ -273,18 +260,18 @@ __global__ __launch_bounds__(kSBlock) void k_split_node_min(SMesh m, const int *
 #pragma unroll
       for (int p = 0; p < 3; p++) {
         const int x = vv[idir(f, p)] - 1;
-        if (!node_pos || node_pos[x] < 0) min64(&nmin[x], base + (u64)(3 * f + p));
+        if (!node_pos || node_pos[x] < 0) atomic_lower(&nmin[x], base + (u64)(3 * f + p));
       }
     }
   }
 }
 
 // The mask word of every new tetra (the header of this file).
-__global__ __launch_bounds__(kSBlock) void k_split_mask(SMesh m, const int *skey, const int *old_tet, const int4 *first,
+__global__ __launch_bounds__(kPBlock) void k_split_mask(SMesh m, const int *skey, const int *old_tet, const int4 *first,
                                                         const int *node_pos, const int *face_old, const u64 *nmin,
                                                         unsigned int *mask) {
-  const int stride = (int)gridDim.x * kSBlock;
-  for (int n = (int)blockIdx.x * kSBlock + (int)threadIdx.x; n < m.ne; n += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int n = (int)blockIdx.x * kPBlock + (int)threadIdx.x; n < m.ne; n += stride) {
     const int k = old_tet[n] - 1, g = skey[n];
     const int4 v = m.tetv[(size_t)k * m.tstride];
     const int vv[4] = {v.x, v.y, v.z, v.w};
@@ -331,7 +318,7 @@ __device__ __forceinline__ void five_prefix(unsigned int w, int *wt, int pre[K_K
 #pragma unroll
   for (int i = 0; i < K_KINDS; i += 2) {
     int t;
-    const int p = block_prefix<kSWaves>(c[i] | (c[i + 1] << 16), wt, &t);
+    const int p = block_prefix<kPWaves>(c[i] | (c[i + 1] << 16), wt, &t);
     pre[i] = p & 0xffff;
     tot[i] = t & 0xffff;
     if (i + 1 < K_KINDS) {
@@ -343,9 +330,9 @@ __device__ __forceinline__ void five_prefix(unsigned int w, int *wt, int pre[K_K
 }
 
 // btot[kind * nblk + b] = the entries of kind `kind` in block b = new tetra 256 b .. 256 b + 255
-__global__ __launch_bounds__(kSBlock) void k_split_block_counts(int ne, int nblk, const unsigned int *mask, int *btot) {
-  __shared__ int wt[kSWaves];
-  const int n = (int)blockIdx.x * kSBlock + (int)threadIdx.x;
+__global__ __launch_bounds__(kPBlock) void k_split_block_counts(int ne, int nblk, const unsigned int *mask, int *btot) {
+  __shared__ int wt[kPWaves];
+  const int n = (int)blockIdx.x * kPBlock + (int)threadIdx.x;
   int pre[K_KINDS], tot[K_KINDS];
   five_prefix(n < ne ? mask[n] : 0u, wt, pre, tot);
   if (threadIdx.x < K_KINDS) {
@@ -357,10 +344,10 @@ __global__ __launch_bounds__(kSBlock) void k_split_block_counts(int ne, int nblk
 }
 
 // pre[kind * (ne + 1) + n] = the entries of that kind before new tetra n; [ne]: all of them
-__global__ __launch_bounds__(kSBlock) void k_split_prefix(int ne, int nblk, const unsigned int *mask, const int *boff,
+__global__ __launch_bounds__(kPBlock) void k_split_prefix(int ne, int nblk, const unsigned int *mask, const int *boff,
                                                           int *pre_out) {
-  __shared__ int wt[kSWaves];
-  const int n = (int)blockIdx.x * kSBlock + (int)threadIdx.x;
+  __shared__ int wt[kPWaves];
+  const int n = (int)blockIdx.x * kPBlock + (int)threadIdx.x;
   int pre[K_KINDS], tot[K_KINDS];
   five_prefix(n < ne ? mask[n] : 0u, wt, pre, tot);
   if (n >= ne) return;
@@ -373,9 +360,9 @@ __global__ __launch_bounds__(kSBlock) void k_split_prefix(int ne, int nblk, cons
 }
 
 // table[g] = {ne, np, nface, nnode} of group g; tot[kind] = the entries of every kind
-__global__ __launch_bounds__(kSBlock) void k_split_table(int ne, int ngrp, const int *teoff, const int *pre, int4 *table,
+__global__ __launch_bounds__(kPBlock) void k_split_table(int ne, int ngrp, const int *teoff, const int *pre, int4 *table,
                                                          int *tot) {
-  const int g = (int)blockIdx.x * kSBlock + (int)threadIdx.x;
+  const int g = (int)blockIdx.x * kPBlock + (int)threadIdx.x;
   if (g > ngrp) return;
   const size_t S = (size_t)ne + 1;
   if (g == ngrp) {
@@ -395,12 +382,12 @@ __device__ __forceinline__ int point_id(int q, const unsigned int *mask, const i
 }
 
 // new_tet, tetv_out, adja_out, tet8_out
-__global__ __launch_bounds__(kSBlock) void k_split_emit(SMesh m, const int *skey, const int *old_tet, const int *pos,
+__global__ __launch_bounds__(kPBlock) void k_split_emit(SMesh m, const int *skey, const int *old_tet, const int *pos,
                                                         const int *teoff, const int4 *first, const unsigned int *mask,
                                                         const int *pre_pt, int *new_tet, int4 *tetv_out,
                                                         int4 *adja_out, int4 *tet8_out) {
-  const int stride = (int)gridDim.x * kSBlock;
-  for (int n = (int)blockIdx.x * kSBlock + (int)threadIdx.x; n < m.ne; n += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int n = (int)blockIdx.x * kPBlock + (int)threadIdx.x; n < m.ne; n += stride) {
     const int k = old_tet[n] - 1, g = skey[n], n0 = teoff[g];
     if (new_tet) new_tet[k] = n - n0 + 1;
     if (!tetv_out && !adja_out && !tet8_out) continue;
@@ -427,7 +414,7 @@ __global__ __launch_bounds__(kSBlock) void k_split_emit(SMesh m, const int *skey
 }
 
 // old_pt, the face lists, and the second run of the node lists with the positions it gives (vpos)
-__global__ __launch_bounds__(kSBlock) void k_split_lists(SMesh m, const int *skey, const int *old_tet, const int *pos,
+__global__ __launch_bounds__(kPBlock) void k_split_lists(SMesh m, const int *skey, const int *old_tet, const int *pos,
                                                          const int *teoff, const int4 *first, const unsigned int *mask,
                                                          const int *pre, const int *face_old, int nnode0, int nface0,
                                                          int *old_pt, int *face_idx1, int *face_idx2, int *node_idx1,
@@ -435,8 +422,8 @@ __global__ __launch_bounds__(kSBlock) void k_split_lists(SMesh m, const int *ske
   const size_t S = (size_t)m.ne + 1;
   const int *pre_pt = pre + K_PT * S, *pre_fe = pre + K_FENT * S, *pre_fo = pre + K_FOWN * S, *pre_n1 = pre + K_N1 * S,
             *pre_n2 = pre + K_N2 * S;
-  const int stride = (int)gridDim.x * kSBlock;
-  for (int n = (int)blockIdx.x * kSBlock + (int)threadIdx.x; n < m.ne; n += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int n = (int)blockIdx.x * kPBlock + (int)threadIdx.x; n < m.ne; n += stride) {
     const unsigned int w = mask[n];
     if (!w) continue;
     const int k = old_tet[n] - 1, g = skey[n], n0 = teoff[g], t = n - n0 + 1;
@@ -491,14 +478,14 @@ __global__ __launch_bounds__(kSBlock) void k_split_lists(SMesh m, const int *ske
 }
 
 // the first run of the node lists: the points of a group that came with a position or got one from a lower colour
-__global__ __launch_bounds__(kSBlock) void k_split_nodes_old(SMesh m, const int *skey, const int *old_tet,
+__global__ __launch_bounds__(kPBlock) void k_split_nodes_old(SMesh m, const int *skey, const int *old_tet,
                                                              const int *teoff, const unsigned int *mask, const int *pre,
                                                              const int *node_pos, const int *vpos, int *node_idx1,
                                                              int *node_idx2) {
   const size_t S = (size_t)m.ne + 1;
   const int *pre_pt = pre + K_PT * S, *pre_n1 = pre + K_N1 * S, *pre_n2 = pre + K_N2 * S;
-  const int stride = (int)gridDim.x * kSBlock;
-  for (int n = (int)blockIdx.x * kSBlock + (int)threadIdx.x; n < m.ne; n += stride) {
+  const int stride = (int)gridDim.x * kPBlock;
+  for (int n = (int)blockIdx.x * kPBlock + (int)threadIdx.x; n < m.ne; n += stride) {
     const unsigned int w = mask[n];
     if (!(w >> M_N1 & 15u)) continue;
     const int n0 = teoff[skey[n]];
@@ -519,22 +506,6 @@ __global__ __launch_bounds__(kSBlock) void k_split_nodes_old(SMesh m, const int 
   }
 }
 
-// out row r = in row src[r] - 1 in pieces of T (8 or 16 bytes), `per` pieces a row
-template <class T>
-__global__ __launch_bounds__(kSBlock) void k_split_gather(long long total, int per, const int *src, const T *in, T *out) {
-  const long long stride = (long long)gridDim.x * kSBlock;
-  for (long long i = (long long)blockIdx.x * kSBlock + threadIdx.x; i < total; i += stride) {
-    const long long r = i / per;
-    const int e = (int)(i - r * per);
-    out[i] = in[(long long)(src[r] - 1) * per + e];
-  }
-}
-
-int grid_for(long long n) {
-  const long long b = (n + kSBlock - 1) / kSBlock;
-  return b < 1 ? 1 : (b > kSMaxBlocks ? kSMaxBlocks : (int)b);
-}
-
 int bits_of(int ngrp) {
   int b = 1;
   while (b < 31 && (1LL << b) < ngrp) b++;
@@ -550,7 +521,7 @@ int pmmg_split_groups(hipStream_t s, const SplitArgs &a, SplitCache *c, char *ms
   *a.nnode_end = a.nnode0;
   *a.nface_end = a.nface0;
   if (ne == 0) return 1;
-  const int nblk = (ne + kSBlock - 1) / kSBlock, grid = grid_for(ne);
+  const int nblk = (ne + kPBlock - 1) / kPBlock, grid = grid_for(ne);
   const size_t S = (size_t)ne + 1;
 
   // scratch (an allocation may synchronise the device: all of it ahead of the first kernel)
@@ -574,12 +545,11 @@ int pmmg_split_groups(hipStream_t s, const SplitArgs &a, SplitCache *c, char *ms
   if (!reserve(c->blocks, K_KINDS * nblk, s, "split_groups: out of device memory (block counts)", msg, msglen)) return 0;
   if (!reserve(c->digits, 256 * ntile, s, "split_groups: out of device memory (digit counts)", msg, msglen)) return 0;
 
-  const SMesh m{ne, np, reinterpret_cast<const int4 *>(a.m.tetv), a.m.tstride,
-                reinterpret_cast<const int4 *>(a.m.adja), a.m.astride, a.part};
+  const SMesh m{rows_of(a.m), np, a.part};
 
   // the refusals: nothing is written to an output before they are known
   DEVCK(hipMemsetAsync(words, 0, W_COUNT * sizeof(int), s));
-  hipLaunchKernelGGL(k_split_check, dim3(grid), dim3(kSBlock), 0, s, m, ngrp, iota, words + W_FLAGS);
+  hipLaunchKernelGGL(k_split_check, dim3(grid), dim3(kPBlock), 0, s, m, ngrp, iota, words + W_FLAGS);
   DEVCK(hipGetLastError());
   int f = 0;
   if (!read_word(s, words + W_FLAGS, &f, msg, msglen)) return 0;
@@ -602,21 +572,21 @@ int pmmg_split_groups(hipStream_t s, const SplitArgs &a, SplitCache *c, char *ms
 
   // the new order
   const int *kin = a.part, *vin = iota;
-  const int tgrid = ntile < kSMaxBlocks ? ntile : kSMaxBlocks;
+  const int tgrid = ntile < kPMaxBlocks ? ntile : kPMaxBlocks;
   for (int i = 0; i < npass; i++) { // (the last pass writes skey and old_tet; the passes before it alternate)
     const bool fin = (npass - 1 - i) % 2 == 0;
     int *kout = fin ? skey : tmpk, *vout = fin ? a.old_tet : tmpv;
-    hipLaunchKernelGGL(k_split_digit_count, dim3(tgrid), dim3(kSBlock), 0, s, ne, 8 * i, ntile, kin,
+    hipLaunchKernelGGL(k_split_digit_count, dim3(tgrid), dim3(kPBlock), 0, s, ne, 8 * i, ntile, kin,
                        c->digits.btot.as<int>());
     DEVCK(hipGetLastError());
     if (!offsets(c->digits, s, 256 * ntile, nullptr, msg, msglen)) return 0;
-    hipLaunchKernelGGL(k_split_digit_scatter, dim3(tgrid), dim3(kSBlock), 0, s, ne, 8 * i, ntile,
+    hipLaunchKernelGGL(k_split_digit_scatter, dim3(tgrid), dim3(kPBlock), 0, s, ne, 8 * i, ntile,
                        c->digits.boff.as<int>(), kin, vin, kout, vout);
     DEVCK(hipGetLastError());
     kin = kout;
     vin = vout;
   }
-  hipLaunchKernelGGL(k_split_places, dim3(grid), dim3(kSBlock), 0, s, ne, ngrp, skey, a.old_tet, pos, teoff);
+  hipLaunchKernelGGL(k_split_places, dim3(grid), dim3(kPBlock), 0, s, ne, ngrp, skey, a.old_tet, pos, teoff);
   DEVCK(hipGetLastError());
 
   // first uses
@@ -630,8 +600,8 @@ int pmmg_split_groups(hipStream_t s, const SplitArgs &a, SplitCache *c, char *ms
     }
     u64 *cur = vmin[r & 1], *nxt = vmin[(r + 1) & 1];
     DEVCK(hipMemsetAsync(words + W_LEFT, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_split_first_min, dim3(grid), dim3(kSBlock), 0, s, m, skey, a.old_tet, first, cur);
-    hipLaunchKernelGGL(k_split_first_settle, dim3(grid), dim3(kSBlock), 0, s, m, skey, a.old_tet, first, cur, nxt,
+    hipLaunchKernelGGL(k_split_first_min, dim3(grid), dim3(kPBlock), 0, s, m, skey, a.old_tet, first, cur);
+    hipLaunchKernelGGL(k_split_first_settle, dim3(grid), dim3(kPBlock), 0, s, m, skey, a.old_tet, first, cur, nxt,
                        words + W_LEFT);
     DEVCK(hipGetLastError());
     c->rounds++;
@@ -643,16 +613,16 @@ int pmmg_split_groups(hipStream_t s, const SplitArgs &a, SplitCache *c, char *ms
   // counts and places
   int *btot = c->blocks.btot.as<int>();
   const int *boff = c->blocks.boff.as<int>();
-  hipLaunchKernelGGL(k_split_node_min, dim3(grid), dim3(kSBlock), 0, s, m, skey, a.old_tet, a.node_pos, nmin);
-  hipLaunchKernelGGL(k_split_mask, dim3(grid), dim3(kSBlock), 0, s, m, skey, a.old_tet, first, a.node_pos, a.face_old,
+  hipLaunchKernelGGL(k_split_node_min, dim3(grid), dim3(kPBlock), 0, s, m, skey, a.old_tet, a.node_pos, nmin);
+  hipLaunchKernelGGL(k_split_mask, dim3(grid), dim3(kPBlock), 0, s, m, skey, a.old_tet, first, a.node_pos, a.face_old,
                      nmin, mask);
-  hipLaunchKernelGGL(k_split_block_counts, dim3(nblk), dim3(kSBlock), 0, s, ne, nblk, mask, btot);
+  hipLaunchKernelGGL(k_split_block_counts, dim3(nblk), dim3(kPBlock), 0, s, ne, nblk, mask, btot);
   DEVCK(hipGetLastError());
   if (!offsets(c->blocks, s, K_KINDS * nblk, nullptr, msg, msglen)) return 0;
-  hipLaunchKernelGGL(k_split_prefix, dim3(nblk), dim3(kSBlock), 0, s, ne, nblk, mask, boff, pre);
-  hipLaunchKernelGGL(k_split_table, dim3((ngrp + 1 + kSBlock - 1) / kSBlock), dim3(kSBlock), 0, s, ne, ngrp, teoff, pre,
+  hipLaunchKernelGGL(k_split_prefix, dim3(nblk), dim3(kPBlock), 0, s, ne, nblk, mask, boff, pre);
+  hipLaunchKernelGGL(k_split_table, dim3((ngrp + 1 + kPBlock - 1) / kPBlock), dim3(kPBlock), 0, s, ne, ngrp, teoff, pre,
                      table, words + W_TOT);
-  hipLaunchKernelGGL(k_split_emit, dim3(grid), dim3(kSBlock), 0, s, m, skey, a.old_tet, pos, teoff, first, mask,
+  hipLaunchKernelGGL(k_split_emit, dim3(grid), dim3(kPBlock), 0, s, m, skey, a.old_tet, pos, teoff, first, mask,
                      pre + K_PT * S, a.new_tet, reinterpret_cast<int4 *>(a.tetv_out),
                      reinterpret_cast<int4 *>(a.adja_out), reinterpret_cast<int4 *>(a.tet8_out));
   DEVCK(hipGetLastError());
@@ -684,26 +654,11 @@ int pmmg_split_groups(hipStream_t s, const SplitArgs &a, SplitCache *c, char *ms
   }
 
   // the lists
-  hipLaunchKernelGGL(k_split_lists, dim3(grid), dim3(kSBlock), 0, s, m, skey, a.old_tet, pos, teoff, first, mask, pre,
+  hipLaunchKernelGGL(k_split_lists, dim3(grid), dim3(kPBlock), 0, s, m, skey, a.old_tet, pos, teoff, first, mask, pre,
                      a.face_old, a.nnode0, a.nface0, a.old_pt, a.face_idx1, a.face_idx2, a.node_idx1, a.node_idx2, vpos);
-  hipLaunchKernelGGL(k_split_nodes_old, dim3(grid), dim3(kSBlock), 0, s, m, skey, a.old_tet, teoff, mask, pre,
+  hipLaunchKernelGGL(k_split_nodes_old, dim3(grid), dim3(kPBlock), 0, s, m, skey, a.old_tet, teoff, mask, pre,
                      a.node_pos, vpos, a.node_idx1, a.node_idx2);
   DEVCK(hipGetLastError());
   DEVCK(hipStreamSynchronize(s));
-  return 1;
-}
-
-int pmmg_split_gather(hipStream_t s, int64_t n, const int *src, int size, const double *in, double *out, char *msg,
-                      size_t msglen) {
-  if (n == 0) return 1;
-  if (size % 2 == 0 && aligned<16>(in) && aligned<16>(out)) {
-    const long long total = (long long)n * (size / 2);
-    hipLaunchKernelGGL(k_split_gather<double2>, dim3(grid_for(total)), dim3(kSBlock), 0, s, total, size / 2, src,
-                       reinterpret_cast<const double2 *>(in), reinterpret_cast<double2 *>(out));
-  } else {
-    const long long total = (long long)n * size;
-    hipLaunchKernelGGL(k_split_gather<double>, dim3(grid_for(total)), dim3(kSBlock), 0, s, total, size, src, in, out);
-  }
-  DEVCK(hipGetLastError());
   return 1;
 }

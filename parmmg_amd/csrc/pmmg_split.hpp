@@ -45,7 +45,3 @@ struct SplitArgs {
   int *nnode_end, *nface_end;
 };
 int pmmg_split_groups(hipStream_t s, const SplitArgs &a, SplitCache *cache, char *msg, size_t msglen);
-
-// out row r = in row src[r] - 1, rows of `size` doubles.  Asynchronous on s.  Returns 1, or 0 with msg set.
-int pmmg_split_gather(hipStream_t s, int64_t n, const int *src, int size, const double *in, double *out, char *msg,
-                      size_t msglen);

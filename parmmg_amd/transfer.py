@@ -46,6 +46,13 @@ def _is_dev(a) -> bool:
     return isinstance(a, DeviceArray) or bool(getattr(a, "is_cuda", False))
 
 
+def _free_all(arrays) -> None:
+    """the outputs a failed call allocated (None: one that was not asked for)"""
+    for a in arrays:
+        if a is not None:
+            a.free()
+
+
 @dataclass
 class DeviceArray:
     ptr: int
@@ -600,13 +607,10 @@ class TransferContext:
             try:
                 self._ck(call(caps, lists), "split_groups")
             except Exception:
-                for a in lists:
-                    a.free()
+                _free_all(lists)
                 raise
         except Exception:
-            for a in out.values():
-                if a is not None:
-                    a.free()
+            _free_all(out.values())
             raise
         c, tot = totals()
         for a, n in zip(lists, (tot[1], tot[2], tot[2], tot[3], tot[3])):  # (a cap may exceed its list)
@@ -621,12 +625,16 @@ class TransferContext:
         """out row r = rows row src[r] - 1 on the device (pmmg_hip_gather_rows):
         src int32 [n] 1-based, rows float64 [m, size].  Returns the DeviceArray
         [n, size] (out, when given)."""
+        return self._gather("gather_rows", np.float64, src, rows, out)
+
+    def _gather(self, name, dtype, src, rows, out):
+        """gather_rows and gather_rows_i32: pmmg_hip_<name> on rows [m] or [m, size] of dtype"""
         if not (_is_dev(src) and _is_dev(rows) and (out is None or _is_dev(out))):
-            raise ValueError("gather_rows takes device arrays")
-        n, size = int(src.shape[0]), int(rows.shape[1])
+            raise ValueError(f"{name} takes device arrays")
+        n, size = int(src.shape[0]), int(rows.shape[1]) if len(rows.shape) > 1 else 1
         if out is None:
-            out = self.empty((n, size), np.float64)
-        self._ck(self.lib.pmmg_hip_gather_rows(self.h, n, _p(src), size, _p(rows), _p(out)), "gather_rows")
+            out = self.empty((n,) + tuple(rows.shape[1:]), dtype)
+        self._ck(getattr(self.lib, "pmmg_hip_" + name)(self.h, n, _p(src), size, _p(rows), _p(out)), name)
         return out
 
     def groups_from_split(self, split, xyz, met=None, fields=()):
@@ -706,9 +714,7 @@ class TransferContext:
             _p(out["new_pt"]), _p(out["new_tet"]), _p(out["src_pt"]), _p(out["src_tet"]), _p(out["tetv_out"]),
             _p(out["mark_out"]), _p(out["node_val"]), _p(out["face_val"]), ctypes.byref(npo), ctypes.byref(neo))
         if not ok:
-            for x in out.values():
-                if x is not None:
-                    x.free()
+            _free_all(out.values())
             err = RuntimeError(f"merge_groups failed: {self.error()}")
             err.np, err.ne = npo.value, neo.value  # (filled when only pt_cap was short)
             raise err
@@ -720,13 +726,7 @@ class TransferContext:
         """gather_rows for int32 rows (pmmg_hip_gather_rows_i32): the ref /
         mark rows of the merged tetra through src_tet.  rows int32 [m] or
         [m, size]; returns the DeviceArray [n] or [n, size] (out, when given)."""
-        if not (_is_dev(src) and _is_dev(rows) and (out is None or _is_dev(out))):
-            raise ValueError("gather_rows_i32 takes device arrays")
-        n, size = int(src.shape[0]), int(rows.shape[1]) if len(rows.shape) > 1 else 1
-        if out is None:
-            out = self.empty((n,) + tuple(rows.shape[1:]), np.int32)
-        self._ck(self.lib.pmmg_hip_gather_rows_i32(self.h, n, _p(src), size, _p(rows), _p(out)), "gather_rows_i32")
-        return out
+        return self._gather("gather_rows_i32", np.int32, src, rows, out)
 
     def merged_from_groups(self, merge, xyz, met=None, fields=()):
         """The point rows of the merged mesh from the groups' (device arrays

@@ -397,6 +397,35 @@ def test_gather_rows_i32(ctx, size, offset):
         free(d_rows, d_src, out)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [1, 2])
+@pytest.mark.parametrize("offset", [0, 8])
+def test_gather_rows_as_doubles_and_as_ints(ctx, size, offset):
+    """the one kernel behind both calls: the same buffer gathered as rows of `size` doubles and as rows of 2 size
+    ints gives the same bytes.  size 2 at offset 0 moves 16-byte pieces in both; size 2 at offset 8 falls back to
+    elements (bases not 16-byte aligned), size 1 is never a multiple of 16 bytes: 8-byte against 4-byte pieces"""
+    rng = np.random.default_rng(10 * size + offset)
+    rows = rng.integers(-2 ** 31, 2 ** 31 - 1, (70, 2 * size)).astype(np.int32)  # (any bit pattern: NaNs among them)
+    d_rows, rows_alloc = device_view(ctx, rows, offset)
+    try:
+        for n in (0, 1, 65):
+            src = rng.integers(1, 71, n).astype(np.int32)
+            d_src, src_alloc = device_view(ctx, src, 4)
+            d_f64, f64_alloc = device_view(ctx, np.full((n, 2 * size), SENT, np.int32), offset)
+            d_i32, i32_alloc = device_view(ctx, np.full((n, 2 * size), SENT, np.int32), offset)
+            assert ctx.lib.pmmg_hip_gather_rows(ctx.h, n, P(d_src), size, P(d_rows), P(d_f64)) == 1, ctx.error()
+            assert ctx.lib.pmmg_hip_gather_rows_i32(ctx.h, n, P(d_src), 2 * size, P(d_rows), P(d_i32)) == 1, ctx.error()
+            as_f64, as_i32 = d_f64.download(), d_i32.download()
+            assert as_f64.tobytes() == as_i32.tobytes()
+            np.testing.assert_array_equal(as_i32, rows[src - 1])
+            for al in (src_alloc, f64_alloc, i32_alloc):
+                al.check("n=%d" % n)
+                al.free()
+        rows_alloc.check("rows")
+    finally:
+        rows_alloc.free()
+
+
 # ---------------------------------------------------------------- 7. chains on the device
 
 @pytest.mark.gpu
